@@ -23,6 +23,12 @@ sends every bucket to its owner; "broadcast" (Option B): each rank's reads
 are broadcast and every rank hashes every k-mer, keeping its own bins'
 updates.  value = all ranks' k-mers / max time.
 
+A plain run sets up, warms up, times the K steps (per-kernel HIP events on:
+the roofline block comes from them), writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line.  --full adds what is beside
+the headline figure: the unprofiled repeat of the K steps, the counters and
+the golden-fixture parity check, and the oracle CPU baseline.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -107,7 +113,19 @@ def parse():
     ap.add_argument("--no-unprofiled", dest="unprofiled", action="store_false",
                     help="skip the second, unprofiled run of the K steps (ms_per_step_unprofiled)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the unprofiled "
+                         "repeat of the K steps, the counters and golden-fixture parity check of the result, and "
+                         "the oracle CPU baseline (a plain run leaves these null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64; tables and per-read outputs larger than the dump budget as a fixed, seeded "
+                         "sample of their elements); one GPU only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.gpus > 1:
+        ap.error("--dump-outputs is for --gpus 1")
     a.graph, k, x = CONFIGS[a.config]
     a.k = k if a.k is None else a.k
     a.x = x if a.x is None else a.x
@@ -359,6 +377,59 @@ def launch_ranks(n):
     return rc if rc >= 0 else 1
 
 
+def full_check(args, runner, rank, world, nreads, progress):
+    """--full: the counters of the last step and the parity of the timed
+    workload itself, when a golden fixture holds it (collective when sharded)."""
+    check_info = runner.check()
+    fx, exact_order = matching_fixture(args, nreads * world,
+                                       (args.group_mode, [world, args.batch_kmers])
+                                       if (args.group_mode != "broadcast" and world > 1) else None)
+    if args.query:
+        # the tables were built untimed from the same reads; the fixture's
+        # get_median_count digest (median, average, stddev of its first
+        # reads).  Medians do not depend on the consume order: the
+        # stream-order fixture of the same reads holds the digest whatever
+        # order the group consumed them in.
+        qfx, _ = matching_fixture(args, nreads * world)
+        if qfx is not None and qfx.get("median_sha256"):
+            q = runner.query_check(qfx)   # collective when sharded
+            if rank == 0:
+                check_info.update(q)
+        elif rank == 0:
+            check_info["median_match"] = "no query fixture for this workload"
+        fx = None
+    if fx is not None:
+        progress("hashing the tables for the %s check" % fx["config"])
+        sha = runner.table_sha256()   # collective when sharded
+        if rank == 0:
+            check_info.update(compare_fixture(fx, check_info["n_unique_kmers"], check_info["n_occupied"], sha,
+                                              stream_order=exact_order))
+    return check_info
+
+
+DUMP_ELEMS = 8 << 20   # elements over all dumped arrays: 32 MiB of float32
+DUMP_SEED = 0x64756d70
+
+
+def sample_indices(n, cap, seed):
+    """Which elements of an n-element output are dumped: all of them (None)
+    up to cap, else cap seeded positions in ascending order (the same for
+    every run with the same n, cap and seed)."""
+    import numpy as np
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=cap, dtype=np.int64))
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output array of the last step."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def main():
     args = parse()
     if args.ablate:
@@ -414,10 +485,14 @@ def main():
     progress("timed steps done")
     stats = runner.kernel_stats()
     runner.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner.outputs())
+        progress("outputs written")
+    # everything below the dump is beside the headline figure: --full only.
     # the same K steps again without the per-kernel HIP events: how much the
     # profiling in the timed region costs (reported, never `value`)
     unprof = None
-    if args.unprofiled:
+    if args.full and args.unprofiled:
         runner.barrier()
         u0 = time.perf_counter()
         for _ in range(args.steps):
@@ -426,31 +501,7 @@ def main():
         u1 = time.perf_counter()
         runner.barrier()
         unprof = runner.max_over_ranks(u1 - u0) * 1e3 / args.steps
-    check_info = runner.check()
-    # parity of the timed workload itself, when a golden fixture holds it
-    fx, exact_order = matching_fixture(args, nreads * world,
-                                       (args.group_mode, [world, args.batch_kmers])
-                                       if (args.group_mode != "broadcast" and world > 1) else None)
-    if args.query:
-        # the tables were built untimed from the same reads; the fixture's
-        # get_median_count digest (median, average, stddev of its first
-        # reads).  Medians do not depend on the consume order: the
-        # stream-order fixture of the same reads holds the digest whatever
-        # order the group consumed them in.
-        qfx, _ = matching_fixture(args, nreads * world)
-        if qfx is not None and qfx.get("median_sha256"):
-            q = runner.query_check(qfx)   # collective when sharded
-            if rank == 0:
-                check_info.update(q)
-        elif rank == 0:
-            check_info["median_match"] = "no query fixture for this workload"
-        fx = None
-    if fx is not None:
-        progress("hashing the tables for the %s check" % fx["config"])
-        sha = runner.table_sha256()   # collective when sharded
-        if rank == 0:
-            check_info.update(compare_fixture(fx, check_info["n_unique_kmers"], check_info["n_occupied"], sha,
-                                              stream_order=exact_order))
+    check_info = full_check(args, runner, rank, world, nreads, progress) if args.full else None
 
     bpk = query_bytes_per_kmer(L, k, nt) if args.query else algorithmic_bytes_per_kmer(L, k, nt)
     total_kmers = nkmers * world * args.steps
@@ -485,7 +536,7 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_reads > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_reads > 0:
         cpu = cpu_baseline(args, sizes)
 
     if rank == 0:
@@ -500,6 +551,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "ms_per_step_unprofiled": unprof,
             "higher_is_better": True,
@@ -633,6 +685,32 @@ class SingleGpuBench(object):
             med, avg, sd = self.query_outputs()
             out["median_sha256"] = FD.median_digest(med, avg, sd)   # medians, averages and stddevs
             out["median_max"] = int(med.max()) if len(med) else 0
+        return out
+
+    def outputs(self):
+        """What the last step left for its caller, as float arrays for
+        --dump-outputs.  consume: every table's raw bytes (table<i>) and the
+        two counters; --query: the per-read median, average and stddev.  An
+        array over its share of DUMP_ELEMS is sampled (sample_indices)."""
+        import numpy as np
+        self._ck(self.lib.kh_device_synchronize(self.device))
+        out = {}
+        if self.args.query:
+            per = DUMP_ELEMS // 3
+            idx = sample_indices(self.args.reads, per, DUMP_SEED)
+            for name, arr in zip(("median", "average", "stddev"), self.query_outputs()):
+                out[name] = (arr if idx is None else arr[idx]).astype(np.float32)
+            return out
+        sizes = self.g._raw_sizes()
+        per = DUMP_ELEMS // len(sizes)
+        for i, n in enumerate(sizes):
+            buf = np.empty(n, np.uint8)
+            self._ck(self.lib.kh_graph_copy_table(self.g._g, i, buf.ctypes.data_as(ctypes.c_void_p)))
+            idx = sample_indices(n, per, DUMP_SEED + i)
+            out["table%d" % i] = (buf if idx is None else buf[idx]).astype(np.float32)
+            del buf
+        out["n_unique_kmers"] = np.array([self.g.n_unique_kmers()], np.float64)
+        out["n_occupied"] = np.array([self.g.n_occupied()], np.float64)
         return out
 
     def query_outputs(self):

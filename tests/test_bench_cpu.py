@@ -117,3 +117,41 @@ def test_auto_group_mode(bench, argv, mode):
     crossover DESIGN.md §6 derives (table bytes against 4 x tables x the
     k-mers of a rank-pass); an explicit --group-mode wins."""
     assert _args(bench, argv).group_mode == mode
+
+
+def test_plain_run_is_the_default(bench):
+    """A plain run does the timed steps only: --full (the unprofiled repeat,
+    the parity check, the CPU baseline) and --dump-outputs are opt-in."""
+    a = _args(bench, ["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = _args(bench, ["--full", "--dump-outputs", "somewhere"])
+    assert (a.full, a.dump_outputs) == (True, "somewhere")
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "d"]])
+def test_rejected_arguments(bench, argv, capsys):
+    with pytest.raises(SystemExit) as e:
+        _args(bench, argv)
+    assert e.value.code == 2
+    capsys.readouterr()
+
+
+def test_sample_indices(bench):
+    np = pytest.importorskip("numpy")
+    assert bench.sample_indices(1000, 1000, 1) is None
+    a = bench.sample_indices(10**9, 4096, 1)
+    assert a.shape == (4096,) and a.dtype == np.int64
+    assert a.min() >= 0 and a.max() < 10**9 and (np.diff(a) >= 0).all()
+    assert (a == bench.sample_indices(10**9, 4096, 1)).all()
+    assert (a != bench.sample_indices(10**9, 4096, 2)).any()
+
+
+def test_dump_outputs_writes_float_npy(bench, tmp_path):
+    np = pytest.importorskip("numpy")
+    d = str(tmp_path / "new" / "dir")
+    bench.dump_outputs(d, {"a": np.arange(5, dtype=np.float32), "b": np.array([2.0**40 + 1])})
+    assert sorted(os.listdir(d)) == ["a.npy", "b.npy"]
+    assert np.load(os.path.join(d, "a.npy")).tolist() == [0, 1, 2, 3, 4]
+    assert np.load(os.path.join(d, "b.npy")).dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(d, {"c": np.zeros(3, np.uint8)})

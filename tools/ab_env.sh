@@ -17,7 +17,7 @@ for r in $(seq 1 "$runs"); do
         envs=()
         IFS=',' read -ra parts <<< "$kv"
         for p in "${parts[@]}"; do [ -n "$p" ] && envs+=("$p"); done
-        env "${envs[@]}" KHMER_AMD_LIB="$lib" timeout -k 10 400 python3 bench.py --cpu-reads 0 "$@" \
+        env "${envs[@]}" KHMER_AMD_LIB="$lib" timeout -k 10 400 python3 bench.py --full --cpu-reads 0 "$@" \
             > $out/$tag$r.json 2> $out/$tag$r.err || exit $?
         python3 - "$tag" $out/$tag$r.json <<'PY'
 import json, sys

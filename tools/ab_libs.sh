@@ -14,7 +14,7 @@ for r in $(seq 1 "$runs"); do
     for c in "${cfgs[@]}"; do
         tag=${c%%=*}; lib=${c#*=}
         if [ -n "$lib" ]; then export KHMER_AMD_LIB=$lib; else unset KHMER_AMD_LIB; fi
-        timeout -k 10 300 python3 bench.py --cpu-reads 0 "$@" > $out/$tag$r.json 2> $out/$tag$r.err || exit $?
+        timeout -k 10 300 python3 bench.py --full --cpu-reads 0 "$@" > $out/$tag$r.json 2> $out/$tag$r.err || exit $?
         python3 - "$tag" $out/$tag$r.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

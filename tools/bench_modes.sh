@@ -12,7 +12,7 @@ out=gpurun_out/modes_$tag
 mkdir -p "$out"
 run() {
     name=$1; shift
-    timeout -k 10 400 python3 bench.py "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "FAIL $name rc=$?"; tail -3 "$out/$name.err"; return 1; }
+    timeout -k 10 400 python3 bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "FAIL $name rc=$?"; tail -3 "$out/$name.err"; return 1; }
     python3 - "$name" "$out/$name.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
