@@ -185,6 +185,35 @@ int kh_graph_kmer_counts(kh_graph *g, const char *seqs, const uint64_t *offsets,
  * Python binding raises ValueError for them, graphs.pyx:182-185). */
 int kh_median_at_least(kh_graph *g, const char *seqs, const uint64_t *offsets, uint64_t nreads, uint32_t cutoff,
                        uint8_t *out, uint8_t *status);
+/* Hashtable::trim_on_abundance (below = 0, src/oxli/hashtable.cc:504-533) or
+ * trim_below_abundance (below = 1, hashtable.cc:535-563) per raw read of a
+ * batch: trim_at[r] = 0 when the read has a single k-mer or its first k-mer
+ * fails (count < cutoff, below: count > cutoff), the end position k + j - 1
+ * of the first failing k-mer j >= 1, else the read's length.  gate != 0 is
+ * khmer/trimming.py:44-46: a read whose median_at_least(normalize_to) is
+ * false is left alone, trim_at[r] = its length (evaluated before the
+ * single-k-mer rule).  Reads shorter than k get status[r] = 1 and
+ * trim_at[r] = 0 (ValueError in the reference's binding, graphs.pyx:197-207). */
+int kh_trim_on_abundance(kh_graph *g, const char *seqs, const uint64_t *offsets, uint64_t nreads, uint16_t cutoff,
+                         int below, int gate, uint32_t normalize_to, uint64_t *trim_at, uint8_t *status);
+/* Hashtable::find_spectral_error_positions (src/oxli/hashtable.cc:565-612) per
+ * raw read of a batch, CSR output: read r's positions are
+ * pos[pos_off[r] .. pos_off[r + 1]) (pos_off holds nreads + 1 entries and is
+ * always written in full).  KH_EVALUE when pos_off[nreads] > cap: pos is then
+ * untouched and pos_off[nreads] is the capacity to call again with.  Reads
+ * shorter than k get status[r] = 1 and no position. */
+int kh_find_spectral_error_positions(kh_graph *g, const char *seqs, const uint64_t *offsets, uint64_t nreads,
+                                     uint16_t max_count, uint64_t *pos_off, uint32_t *pos, uint64_t cap,
+                                     uint8_t *status);
+/* kh_trim_on_abundance over device-resident fixed-length reads, one wave per
+ * read, d_trim_at[nreads] in device memory.  The input rules of
+ * kh_median_counts_fixed_device apply: read_len >= k, read_len - k + 1 <= 256,
+ * 2-bit packed words for 2-bit graphs, ASCII bytes (with the padding rule of
+ * kh_consume_bytes_fixed_device) for Murmur graphs.  Replaces the per-read
+ * loop of scripts/filter-abund.py:154-162 over khmer/trimming.py:38-67
+ * (src/oxli/hashtable.cc:333-364, 504-563). */
+int kh_trim_fixed_device(kh_graph *g, const void *d_reads, uint64_t nreads, uint32_t read_len, uint16_t cutoff,
+                         int below, int gate, uint32_t normalize_to, uint32_t *d_trim_at);
 /* Hashtable::abundance_distribution (src/oxli/hashtable.cc:451-493);
  * dist[65536]. */
 int kh_abundance_distribution(kh_graph *g, kh_parser *p, kh_graph *tracking, uint64_t *dist);

@@ -93,6 +93,11 @@ SIGNATURES = {
     "kh_graph_kmer_counts": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.POINTER(ctypes.c_uint16), PU64]),
     "kh_median_at_least": (i32, [P, ctypes.c_char_p, PU64, u64, u32, ctypes.POINTER(ctypes.c_uint8),
                                  ctypes.POINTER(ctypes.c_uint8)]),
+    "kh_trim_on_abundance": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.c_uint16, i32, i32, u32, PU64,
+                                   ctypes.POINTER(ctypes.c_uint8)]),
+    "kh_find_spectral_error_positions": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.c_uint16, PU64, PU32, u64,
+                                               ctypes.POINTER(ctypes.c_uint8)]),
+    "kh_trim_fixed_device": (i32, [P, P, u64, u32, ctypes.c_uint16, i32, i32, u32, P]),
     "kh_abundance_distribution": (i32, [P, P, P, PU64]),
     "kh_graph_table_nbytes": (i32, [P, i32, PU64]),
     "kh_graph_copy_table": (i32, [P, i32, ctypes.c_void_p]),

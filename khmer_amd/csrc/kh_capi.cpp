@@ -1037,6 +1037,74 @@ int kh_median_at_least(kh_graph *h, const char *seqs, const uint64_t *offsets, u
     });
 }
 
+int kh_trim_on_abundance(kh_graph *h, const char *seqs, const uint64_t *offsets, uint64_t nreads, uint16_t cutoff,
+                         int below, int gate, uint32_t normalize_to, uint64_t *trim_at, uint8_t *status) {
+    return guard([&] {
+        CHECK_PTR(h);
+        Graph *g = h->g;
+        std::lock_guard<std::recursive_mutex> lk(g->mu);
+        KH_HIP(hipSetDevice(g->device));
+        HostBatch b;
+        std::vector<uint64_t> idx;
+        raw_batch(g, seqs, offsets, nreads, b, idx, status);
+        for (uint64_t r = 0; r < nreads; r++) trim_at[r] = 0;
+        if (!b.nreads()) return;
+        TrimArgs a;
+        a.cutoff = cutoff;
+        a.below = below ? 1 : 0;
+        a.gate = gate ? 1 : 0;
+        a.normalize_to = normalize_to;
+        std::vector<uint64_t> res(b.nreads());
+        engine_trim(g, b, a, res.data());
+        for (size_t t = 0; t < idx.size(); t++) trim_at[idx[t]] = res[t];
+    });
+}
+
+int kh_find_spectral_error_positions(kh_graph *h, const char *seqs, const uint64_t *offsets, uint64_t nreads,
+                                     uint16_t max_count, uint64_t *pos_off, uint32_t *pos, uint64_t cap,
+                                     uint8_t *status) {
+    return guard([&] {
+        CHECK_PTR(h);
+        Graph *g = h->g;
+        std::lock_guard<std::recursive_mutex> lk(g->mu);
+        KH_HIP(hipSetDevice(g->device));
+        HostBatch b;
+        std::vector<uint64_t> idx;
+        raw_batch(g, seqs, offsets, nreads, b, idx, status);
+        std::vector<uint32_t> npos(b.nreads()), win(b.nkmers());
+        engine_spectral(g, b, max_count, npos.data(), win.data());
+        // CSR offsets over all reads (short reads: empty), then the windows compacted
+        pos_off[0] = 0;
+        size_t t = 0;
+        for (uint64_t r = 0; r < nreads; r++) {
+            const bool in = t < idx.size() && idx[t] == r;
+            pos_off[r + 1] = pos_off[r] + (in ? npos[t] : 0);
+            if (in) t++;
+        }
+        if (pos_off[nreads] > cap) fail(KH_EVALUE, "position buffer too small");
+        for (t = 0; t < idx.size(); t++) {
+            const uint32_t *w = win.data() + b.koff[t];
+            std::copy(w, w + npos[t], pos + pos_off[idx[t]]);
+        }
+    });
+}
+
+int kh_trim_fixed_device(kh_graph *h, const void *d_reads, uint64_t nreads, uint32_t read_len, uint16_t cutoff,
+                         int below, int gate, uint32_t normalize_to, uint32_t *d_trim_at) {
+    return guard([&] {
+        CHECK_PTR(h);
+        Graph *g = h->g;
+        std::lock_guard<std::recursive_mutex> lk(g->mu);
+        KH_HIP(hipSetDevice(g->device));
+        TrimArgs a;
+        a.cutoff = cutoff;
+        a.below = below ? 1 : 0;
+        a.gate = gate ? 1 : 0;
+        a.normalize_to = normalize_to;
+        engine_trim_fixed_device(g, d_reads, nreads, read_len, a, d_trim_at);
+    });
+}
+
 int kh_abundance_distribution(kh_graph *h, kh_parser *ph, kh_graph *th, uint64_t *dist) {
     return guard([&] {
         CHECK_PTR(h);

@@ -1996,6 +1996,78 @@ void engine_median_fixed_device(Graph *g, const void *d_reads, uint64_t nreads, 
     engine_collect_events(g);
 }
 
+// Hashtable::trim_on_abundance / trim_below_abundance
+// (src/oxli/hashtable.cc:504-563) over device-resident fixed-length reads, with
+// khmer/trimming.py's median_at_least gate; the same input rules and pieces as
+// engine_median_fixed_device
+void engine_trim_fixed_device(Graph *g, const void *d_reads, uint64_t nreads, uint64_t read_len, const TrimArgs &a,
+                              uint32_t *d_trim_at) {
+    if (read_len < (uint64_t)g->k) fail(KH_EVALUE, "reads shorter than k");
+    const uint64_t kpr = read_len - g->k + 1;
+    if (kpr > 256) fail(KH_EVALUE, "device trim path takes at most 256 k-mers per read");
+    if (!nreads) return;
+    engine_sync_bigcounts(g);
+    const uint32_t min_req = median_min_req(kpr);
+    if (g->hash == MURMUR) {
+        const uint64_t cr = 1ull << 24;
+        for (uint64_t r0 = 0; r0 < nreads; r0 += cr) {
+            const uint64_t n = std::min(cr, nreads - r0);
+            const uint8_t *rd = padded_bytes(g, (const uint8_t *)d_reads + r0 * read_len, n * read_len);
+            SrcBytes s = src_bytes(g, rd, nullptr, n, kpr, n * read_len);
+            set_fixed(s, kpr, n);
+            const unsigned gr = (unsigned)std::min<uint64_t>((n + 3) / 4, 8192);
+            TIMED("trim", hipLaunchKernelGGL(k_trim_fixed<SrcBytes>, dim3(gr), dim3(256), 0, g->stream, g->prm, s, n,
+                                             (uint32_t)kpr, g->k, g->d_tab, g->d_bc_keys, g->d_bc_vals, g->d_bc_n,
+                                             a.cutoff, a.below, a.gate, a.normalize_to, min_req, d_trim_at + r0));
+        }
+    } else {
+        SrcTwoBit s = src_twobit(g, (const uint64_t *)d_reads);
+        set_fixed(s, kpr, nreads);
+        const unsigned grid = (unsigned)std::min<uint64_t>((nreads + 3) / 4, 8192);
+        TIMED("trim", hipLaunchKernelGGL(k_trim_fixed<SrcTwoBit>, dim3(grid), dim3(256), 0, g->stream, g->prm, s,
+                                         nreads, (uint32_t)kpr, g->k, g->d_tab, g->d_bc_keys, g->d_bc_vals, g->d_bc_n,
+                                         a.cutoff, a.below, a.gate, a.normalize_to, min_req, d_trim_at));
+    }
+    KH_HIP(hipGetLastError());
+    KH_HIP(hipStreamSynchronize(g->stream));
+    engine_collect_events(g);
+}
+
+// the same per read of a host batch (one thread per read over its counts)
+void engine_trim(Graph *g, const HostBatch &b, const TrimArgs &a, uint64_t *h_out) {
+    const uint64_t nk = b.nkmers(), nr = b.nreads();
+    if (!nr) return;
+    engine_sync_bigcounts(g);
+    upload_batch(g, b);
+    DevBuf b_counts(nk * 2 + 64), b_out(nr * 8 + 64);
+    batch_counts(g, b, b_counts.as<uint16_t>());
+    const unsigned grid = (unsigned)std::min<uint64_t>((nr + 255) / 256, 65536);
+    hipLaunchKernelGGL(k_trim, dim3(grid), dim3(256), 0, g->stream, g->ws.d_koff, nr, b_counts.as<uint16_t>(), g->k,
+                       a.cutoff, a.below, a.gate, a.normalize_to, b_out.as<uint64_t>());
+    KH_HIP(hipGetLastError());
+    KH_HIP(hipMemcpyAsync(h_out, b_out.p, nr * 8, hipMemcpyDeviceToHost, g->stream));
+    KH_HIP(hipStreamSynchronize(g->stream));
+}
+
+// Hashtable::find_spectral_error_positions (src/oxli/hashtable.cc:565-612) per
+// read of a host batch: h_npos[r] positions in h_pos[koff[r] ..] (h_pos holds
+// one entry per k-mer of the batch; the caller compacts the windows)
+void engine_spectral(Graph *g, const HostBatch &b, uint32_t max_count, uint32_t *h_npos, uint32_t *h_pos) {
+    const uint64_t nk = b.nkmers(), nr = b.nreads();
+    if (!nr) return;
+    engine_sync_bigcounts(g);
+    upload_batch(g, b);
+    DevBuf b_counts(nk * 2 + 64), b_pos(nk * 4 + 64), b_npos(nr * 4 + 64);
+    batch_counts(g, b, b_counts.as<uint16_t>());
+    const unsigned grid = (unsigned)std::min<uint64_t>((nr + 255) / 256, 65536);
+    hipLaunchKernelGGL(k_spectral, dim3(grid), dim3(256), 0, g->stream, g->ws.d_koff, nr, b_counts.as<uint16_t>(),
+                       g->k, max_count, b_pos.as<uint32_t>(), b_npos.as<uint32_t>());
+    KH_HIP(hipGetLastError());
+    KH_HIP(hipMemcpyAsync(h_npos, b_npos.p, nr * 4, hipMemcpyDeviceToHost, g->stream));
+    if (nk) KH_HIP(hipMemcpyAsync(h_pos, b_pos.p, nk * 4, hipMemcpyDeviceToHost, g->stream));
+    KH_HIP(hipStreamSynchronize(g->stream));
+}
+
 void engine_consume_bytes_fixed(Graph *g, const uint8_t *d_bytes, uint64_t nreads, uint64_t read_len) {
     if (read_len < (uint64_t)g->k) fail(KH_EVALUE, "reads shorter than k");
     const uint64_t kpr = read_len - g->k + 1;

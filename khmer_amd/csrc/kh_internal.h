@@ -387,6 +387,19 @@ void engine_median_at_least(Graph *g, const HostBatch &b, uint32_t cutoff, uint8
 void engine_hash_batch(Graph *g, const HostBatch &b, uint64_t *h_out);
 void engine_median_fixed_device(Graph *g, const void *d_reads, uint64_t nreads, uint64_t read_len, uint16_t *d_med,
                                 float *d_avg, float *d_sd);
+// trim_on_abundance (below = 0: a k-mer fails when count < cutoff) or
+// trim_below_abundance (below = 1: count > cutoff); gate: only reads with
+// median_at_least(normalize_to) are trimmed (khmer/trimming.py:38-67)
+struct TrimArgs {
+    uint32_t cutoff = 0;
+    int below = 0;
+    int gate = 0;
+    uint32_t normalize_to = 0;
+};
+void engine_trim(Graph *g, const HostBatch &b, const TrimArgs &a, uint64_t *h_out);
+void engine_spectral(Graph *g, const HostBatch &b, uint32_t max_count, uint32_t *h_npos, uint32_t *h_pos);
+void engine_trim_fixed_device(Graph *g, const void *d_reads, uint64_t nreads, uint64_t read_len, const TrimArgs &a,
+                              uint32_t *d_trim_at);
 void engine_consume_bytes_fixed(Graph *g, const uint8_t *d_bytes, uint64_t nreads, uint64_t read_len);
 void engine_unpack_ascii(int device, const uint64_t *d_words, uint64_t nbases, uint8_t *d_bytes);
 void engine_sync_bigcounts(Graph *g);

@@ -1,5 +1,6 @@
 // kh_query.cuh -- read-only device kernels: get_count, k-mer hashes/counts,
-// get_median_count, batch boundaries, synthetic reads.  Included by kh_engine.hip.
+// get_median_count, abundance trimming, batch boundaries, synthetic reads.
+// Included by kh_engine.hip.
 #pragma once
 #include "kh_src.cuh"
 
@@ -306,6 +307,121 @@ __global__ void __launch_bounds__(256) k_median_fixed(Params P, Src src, uint64_
             avg[r] = average;
             sd[r] = var;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Abundance trimming (src/oxli/hashtable.cc:504-612) over the counts c[0..n-1]
+// of a read's k-mers.  Both k-mer iterators are done() after k-mer n-1 and
+// report start = j, end = k + j after k-mer j (kmer_hash.hh:364-377, 469-479),
+// so the reference's loops reduce to:
+//   trim_on_abundance / trim_below_abundance: 0 when n <= 1 or c[0] fails,
+//   k + j - 1 for the first failing j >= 1, else the read's length; a k-mer
+//   fails when c < cutoff (on) or c > cutoff (below).
+//   find_spectral_error_positions: t0 = the first j <= n-2 with c[j] > M; none:
+//   no positions; else t0 - 1 (when t0 > 0), then k + s - 1 for the start s of
+//   every maximal run of c[j] <= M after t0.
+// The gate is khmer/trimming.py:44-46: a read whose median_at_least(gate_cut)
+// is false is left alone, reported as trim_at = its length.  min_req(n) is
+// k_at_least's float32 formula.
+__host__ __device__ __forceinline__ uint32_t median_min_req(uint64_t n) {
+    return (uint32_t)(0.5 + (double)((float)n / 2.0f));
+}
+
+// one thread per read of a host batch (counts / koff as for k_at_least)
+__global__ void k_trim(const uint64_t *koff, uint64_t nreads, const uint16_t *counts, int k, uint32_t cutoff,
+                       int below, int gate, uint32_t gate_cut, uint64_t *trim_at) {
+    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < nreads;
+         r += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t a = koff[r], n = koff[r + 1] - a;
+        const uint64_t len = n + (uint64_t)k - 1;
+        if (gate) {
+            uint64_t num = 0;
+            for (uint64_t t = 0; t < n; t++) num += (uint32_t)counts[a + t] >= gate_cut ? 1 : 0;
+            if (num < median_min_req(n)) {
+                trim_at[r] = len;
+                continue;
+            }
+        }
+        uint64_t out = len;
+        if (n <= 1) {
+            out = 0;
+        } else {
+            for (uint64_t t = 0; t < n; t++) {
+                const uint32_t c = counts[a + t];
+                if (below ? c > cutoff : c < cutoff) {
+                    out = t ? (uint64_t)k + t - 1 : 0;
+                    break;
+                }
+            }
+        }
+        trim_at[r] = out;
+    }
+}
+
+// one thread per read: read r's positions go into the n_r-entry window of
+// `pos` at koff[r] (at most n_r / 2 + 1 of them), their number into npos[r]
+__global__ void k_spectral(const uint64_t *koff, uint64_t nreads, const uint16_t *counts, int k, uint32_t max_count,
+                           uint32_t *pos, uint32_t *npos) {
+    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < nreads;
+         r += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t a = koff[r], n = koff[r + 1] - a;
+        uint32_t m = 0;
+        uint64_t t0 = n;
+        for (uint64_t t = 0; t + 1 < n; t++)
+            if ((uint32_t)counts[a + t] > max_count) {
+                t0 = t;
+                break;
+            }
+        if (t0 < n) {
+            if (t0 > 0) pos[a + m++] = (uint32_t)(t0 - 1);
+            bool prev_bad = false;
+            for (uint64_t t = t0 + 1; t < n; t++) {
+                const bool bad = (uint32_t)counts[a + t] <= max_count;
+                if (bad && !prev_bad) pos[a + m++] = (uint32_t)((uint64_t)k + t - 1);
+                prev_bad = bad;
+            }
+        }
+        npos[r] = m;
+    }
+}
+
+// trim_on_abundance / trim_below_abundance over fixed-length device reads, one
+// wave per read, k_median_fixed's layout (kpr <= 256, lane l slot s holds
+// k-mer t = l + 64 s).  Per slot one ballot of the fail predicate and one of
+// the gate predicate; slots past kpr contribute to neither.  The first failing
+// k-mer is the lowest set bit of the first non-empty mask in slot order.
+template <class Src>
+__global__ void __launch_bounds__(256) k_trim_fixed(Params P, Src src, uint64_t nreads, uint32_t kpr, int k,
+                                                    const uint8_t *tab, const uint64_t *bc_keys,
+                                                    const uint16_t *bc_vals, uint64_t bc_n, uint32_t cutoff,
+                                                    int below, int gate, uint32_t gate_cut, uint32_t min_req,
+                                                    uint32_t *trim_at) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint32_t len = kpr + (uint32_t)k - 1;
+    for (uint64_t r = wave; r < nreads; r += nwaves) {
+        uint64_t failm[4];
+        uint32_t num = 0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const uint32_t t = lane + 64u * s;
+            const bool ok = t < kpr;
+            uint32_t c = 0;
+            if (ok) c = get_count_dev(P, tab, kmer_hash_global(src, r * kpr + t), bc_keys, bc_vals, bc_n);
+            failm[s] = __ballot(ok && (below ? c > cutoff : c < cutoff));
+            num += __popcll(__ballot(ok && c >= gate_cut));
+        }
+        uint32_t first = kpr;   // no k-mer fails
+#pragma unroll
+        for (int s = 3; s >= 0; s--)
+            if (failm[s]) first = 64u * s + (uint32_t)__builtin_ctzll(failm[s]);
+        uint32_t out;
+        if (gate && num < min_req) out = len;
+        else if (kpr <= 1 || first == 0) out = 0;
+        else out = first < kpr ? (uint32_t)k + first - 1 : len;
+        if (lane == 0) trim_at[r] = out;
     }
 }
 

@@ -294,6 +294,72 @@ class Hashtable(object):
                                      out, st))
         return [None if st[i] else bool(out[i]) for i in range(n)]
 
+    # ---- abundance trimming (graphs.pyx:197-214) ----
+    @staticmethod
+    def _pack_reads(sequences):
+        datas = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in sequences]
+        offs = [0]
+        for d in datas:
+            offs.append(offs[-1] + len(d))
+        return datas, offs
+
+    def trim_on_abundance(self, sequence, abundance):
+        """The prefix of sequence before its first k-mer rarer than abundance
+        (Hashtable::trim_on_abundance, src/oxli/hashtable.cc:504-533, on the
+        device): (sequence[:pos], pos)."""
+        self._valid_sequence(sequence)
+        pos = self.trim_on_abundance_batch([sequence], abundance)[0]
+        return sequence[:pos], pos
+
+    def trim_below_abundance(self, sequence, abundance):
+        """The prefix of sequence before its first k-mer more frequent than
+        abundance (Hashtable::trim_below_abundance, src/oxli/hashtable.cc:535-563)."""
+        self._valid_sequence(sequence)
+        pos = self.trim_on_abundance_batch([sequence], abundance, below=True)[0]
+        return sequence[:pos], pos
+
+    def trim_on_abundance_batch(self, sequences, abundance, below=False, normalize_to=None):
+        """Trim positions of many reads in one device pass: trim_on_abundance,
+        or trim_below_abundance with `below`.  With `normalize_to` a read whose
+        median_at_least(normalize_to) is false is left alone (its length is
+        returned), as khmer.trimming.trim_record does under
+        variable_coverage.  `abundance` is converted as the reference's
+        BoundedCounterType.  Reads shorter than k give None."""
+        datas, offs = self._pack_reads(sequences)
+        n = len(datas)
+        if not n:
+            return []
+        out = (ctypes.c_uint64 * n)()
+        st = (ctypes.c_uint8 * n)()
+        gate = normalize_to is not None
+        check(lib.kh_trim_on_abundance(self._g, b"".join(datas), _u64_array(offs), n, int(abundance) & 0xFFFF,
+                                       1 if below else 0, 1 if gate else 0,
+                                       int(normalize_to) & 0xFFFFFFFF if gate else 0, out, st))
+        return [None if st[i] else out[i] for i in range(n)]
+
+    def find_spectral_error_positions(self, sequence, max_count):
+        """Positions in sequence where runs of k-mers no more frequent than
+        max_count begin or end
+        (Hashtable::find_spectral_error_positions, src/oxli/hashtable.cc:565-612,
+        on the device)."""
+        self._valid_sequence(sequence)
+        return self.find_spectral_error_positions_batch([sequence], max_count)[0]
+
+    def find_spectral_error_positions_batch(self, sequences, max_count):
+        """find_spectral_error_positions over many reads in one device pass:
+        a list of positions per read, None for reads shorter than k."""
+        datas, offs = self._pack_reads(sequences)
+        n = len(datas)
+        if not n:
+            return []
+        cap = max(offs[-1], 1)     # a read has fewer positions than bases
+        poff = (ctypes.c_uint64 * (n + 1))()
+        pos = (ctypes.c_uint32 * cap)()
+        st = (ctypes.c_uint8 * n)()
+        check(lib.kh_find_spectral_error_positions(self._g, b"".join(datas), _u64_array(offs), n,
+                                                   int(max_count) & 0xFFFF, poff, pos, cap, st))
+        return [None if st[i] else list(pos[poff[i]:poff[i + 1]]) for i in range(n)]
+
     # ---- files of reads (graphs.pyx:216-296) ----
     def _get_parser(self, parser_or_filename):
         if isinstance(parser_or_filename, ReadParser):

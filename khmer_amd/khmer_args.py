@@ -346,3 +346,59 @@ def check_space_for_graph(outfile_name, hash_size, force, _testhook_free_space=N
         else:
             raise SystemExit("ERROR: " + msg +
                              "\nNOTE: This can be overridden using the --force argument")
+
+
+def check_space(in_files, force, _testhook_free_space=None):
+    """Exit when the outputs (estimated at the inputs' size) will not fit on
+    the disk of the first input (khmer/kfile.py:109-149)."""
+    st = os.statvfs(os.path.dirname(os.path.realpath(in_files[0])))
+    free = st.f_frsize * st.f_bavail if _testhook_free_space is None else _testhook_free_space
+    total = sum(os.stat(f).st_size for f in in_files if os.path.isfile(f))
+    short = total - free
+    if short > 0:
+        msg = ("Not enough free space on disk for output files;"
+               "\n       Need at least {:.1f} GB more."
+               "\n       Estimated Output size: {:.1f} GB"
+               "\n       Free space: {:.1f} GB").format(short / 1e9, total / 1e9, free / 1e9)
+        if force:
+            print("WARNING:", msg, file=sys.stderr)
+        else:
+            raise SystemExit("ERROR: " + msg +
+                             "\nNOTE: This can be overridden using the --force argument")
+
+
+# ---------------------------------------------------------------------------
+# option helpers of the filtering scripts
+
+
+def check_argument_range(low, high, parameter_name):
+    """argparse type: an int in [low, high), else the reference's message and
+    exit status 1 (khmer_args.py:275-287)."""
+    def _in_range(value):
+        value = int(value)
+        if not low <= value < high:
+            print("\n** ERROR: khmer only supports %i <= %s < %i.\n" % (low, parameter_name, high),
+                  file=sys.stderr)
+            sys.exit(1)
+        return value
+    return _in_range
+
+
+def add_output_compression_type(parser):
+    """--gzip / --bzip, mutually exclusive (khmer/kfile.py:225-231)."""
+    group = parser.add_mutually_exclusive_group()
+    group.add_argument("--gzip", default=False, action="store_true", help="gzip the output")
+    group.add_argument("--bzip", default=False, action="store_true", help="bzip2 the output")
+
+
+def get_file_writer(file_handle, do_gzip, do_bzip):
+    """file_handle, or a compressing writer over it (khmer/kfile.py:234-248)."""
+    if do_gzip and do_bzip:
+        raise ValueError("Cannot specify both bzip and gzip compression!")
+    if do_gzip:
+        import gzip
+        return gzip.GzipFile(fileobj=file_handle, mode="w")
+    if do_bzip:
+        import bz2
+        return bz2.open(file_handle, mode="w")
+    return file_handle

@@ -1,9 +1,12 @@
-"""The two drop-in scripts on the hot path, as importable functions.
+"""The drop-in scripts on the hot path, as importable functions.
 
 `load_into_counting(argv)` is scripts/load-into-counting.py
-(reference scripts/load-into-counting.py:60-218) and `load_graph(argv)` is
+(reference scripts/load-into-counting.py:60-218), `load_graph(argv)` is
 scripts/load-graph.py (reference scripts/load-graph.py + oxli/build_graph.py:
-40-123).  Options, stderr messages, the saved table, the `.info` file, the
+40-123) and `filter_abund(argv)` is scripts/filter-abund.py (reference
+scripts/filter-abund.py:68-168; it trims FILTER_BATCH_READS reads per device
+pass instead of one call per read, and spools stdin to a temporary file).
+Options, stderr messages, the saved table, the `.info` file, the
 `.info.json` / `.info.tsv` summaries and the `.tagset` file match the
 reference's.  Each input file is consumed as the reference does it: `-T`
 Python threads all call consume_seqfile[_and_tag] on one shared ReadParser
@@ -17,7 +20,9 @@ the files under scripts/ are two-line wrappers.
 """
 import json
 import os
+import shutil
 import sys
+import tempfile
 import threading
 
 from . import khmer_args as KA
@@ -226,6 +231,131 @@ def load_graph(argv=None):
     print("wrote to " + base + ".info and " + base, file=err)
     if not args.no_build_tagset:
         print("and " + base + ".tagset", file=err)
+    return 0
+
+
+# ---------------------------------------------------------------------------
+# filter-abund.py
+
+DEFAULT_NORMALIZE_LIMIT = 20
+DEFAULT_CUTOFF = 2
+FILTER_BATCH_READS = 1 << 16     # reads per device pass of filter_abund
+
+_FA_EPILOG = """\
+    Every input file gets its own output, named after the input's base name
+    plus ``.abundfilt`` and written to the working directory, unless -o names
+    one file for all of them.  Use --variable-coverage for data of uneven
+    coverage (transcriptomes, metagenomes).
+
+    Example:
+
+        load-into-counting.py -k 20 -x 5e7 countgraph reads.fa
+        filter-abund.py -C 2 countgraph reads.fa
+    """
+
+
+def filter_abund_parser():
+    parser = KA.KhmerArgumentParser(description="Trim reads at their first k-mer of low abundance.",
+                                    epilog=KA.dedent(_FA_EPILOG), citations=["counting"])
+    parser.prog = "filter-abund.py"
+    parser.add_argument("input_graph", metavar="input_count_graph_filename",
+                        help="countgraph file written by load-into-counting.py")
+    parser.add_argument("input_filename", metavar="input_sequence_filename", nargs="+",
+                        help="FASTA / FASTQ file of reads to trim")
+    KA.add_threading_args(parser)
+    parser.add_argument("-C", "--cutoff", dest="cutoff", default=DEFAULT_CUTOFF,
+                        type=KA.check_argument_range(0, 256, "cutoff"),
+                        help="cut a read at its first k-mer counted fewer times than this")
+    parser.add_argument("-V", "--variable-coverage", action="store_true", dest="variable_coverage",
+                        default=False,
+                        help="leave reads alone unless their median k-mer count reaches -Z")
+    parser.add_argument("-Z", "--normalize-to", type=int, dest="normalize_to", default=DEFAULT_NORMALIZE_LIMIT,
+                        help="median k-mer count from which -V lets a read be trimmed")
+    parser.add_argument("-o", "--output", dest="single_output_file", metavar="optional_output_filename",
+                        help="write every input's reads to this one file ('-': stdout)")
+    parser.add_argument("-f", "--force", default=False, action="store_true",
+                        help="go on past missing inputs and a full disk")
+    parser.add_argument("-q", "--quiet", dest="quiet", default=False, action="store_true")
+    KA.add_output_compression_type(parser)
+    return parser
+
+
+def write_record(record, fileobj):
+    """FASTA, or FASTQ for a record with a quality (khmer/utils.py:120-135)."""
+    if getattr(record, "quality", None) is not None:
+        recstr = "@{}\n{}\n+\n{}\n".format(record.name, record.sequence, record.quality)
+    else:
+        recstr = ">{}\n{}\n".format(record.name, record.sequence)
+    fileobj.write(recstr.encode("ascii"))
+
+
+def filter_abund(argv=None):
+    import khmer_amd
+    from .trimming import trim_records
+    args = filter_abund_parser().parse_args(argv)
+    KA.configure_logging(args.quiet)
+
+    infiles = args.input_filename
+    if ("-" in infiles or "/dev/stdin" in infiles) and not args.single_output_file:
+        KA.log_error("Accepting input from stdin; output filename must be provided with -o.")
+        sys.exit(1)
+    for filename in infiles:
+        KA.check_input_files(filename, args.force)
+    KA.check_space(infiles, args.force)
+
+    KA.log_info("loading countgraph: {graph}", graph=args.input_graph)
+    countgraph = khmer_amd.Countgraph.load(args.input_graph)
+    ksize = countgraph.ksize()
+    KA.log_info("K: {ksize}", ksize=ksize)
+
+    def open_out(name):
+        raw = sys.stdout.buffer if name == "-" else open(name, "wb")
+        return raw, KA.get_file_writer(raw, args.gzip, args.bzip)
+
+    def filter_batch(batch, outfp):
+        for rec, _ in trim_records(countgraph, batch, args.cutoff, args.variable_coverage, args.normalize_to):
+            if rec:
+                write_record(rec, outfp)
+
+    def close_out(raw, outfp):
+        if outfp is not raw:
+            outfp.close()        # the compressor's trailer
+        if raw is not sys.stdout.buffer:
+            raw.close()
+        else:
+            raw.flush()
+
+    if args.single_output_file:
+        outfile = args.single_output_file
+        raw, outfp = open_out(outfile)
+    for infile in infiles:
+        KA.log_info("filtering {infile}", infile=infile)
+        if not args.single_output_file:
+            outfile = os.path.basename(infile) + ".abundfilt"
+            raw, outfp = open_out(outfile)
+        spool = None
+        if infile in ("-", "/dev/stdin"):    # the parser wants a file it can reopen: spool the pipe
+            spool = tempfile.NamedTemporaryFile(prefix="filter-abund-stdin-")
+            shutil.copyfileobj(sys.stdin.buffer, spool)
+            spool.flush()
+        parser = khmer_amd.ReadParser(spool.name if spool else infile)
+        batch = []
+        for read in parser:
+            if len(read.sequence) < ksize:   # broken_paired_reader(min_length=ksize, force_single=True)
+                continue
+            batch.append(read)
+            if len(batch) >= FILTER_BATCH_READS:
+                filter_batch(batch, outfp)
+                batch = []
+        filter_batch(batch, outfp)
+        parser.close()
+        if spool:
+            spool.close()
+        if not args.single_output_file:
+            close_out(raw, outfp)
+        KA.log_info("output in {outfile}", outfile=outfile)
+    if args.single_output_file:
+        close_out(raw, outfp)
     return 0
 
 
