@@ -185,6 +185,26 @@ int kh_graph_kmer_counts(kh_graph *g, const char *seqs, const uint64_t *offsets,
  * Python binding raises ValueError for them, graphs.pyx:182-185). */
 int kh_median_at_least(kh_graph *g, const char *seqs, const uint64_t *offsets, uint64_t nreads, uint32_t cutoff,
                        uint8_t *out, uint8_t *status);
+/* Digital normalization, the per-unit loop of scripts/normalize-by-median.py:155-179
+ * (Normalizer.__call__ over khmer/utils.py:171-180 broken_paired_reader's
+ * units): a unit is one read, or reads r and r + 1 when pair_with_next[r] = 1
+ * (pair_with_next may be NULL: single reads).  For each unit in order every
+ * read is tested with median_at_least(cutoff) against the table as it stands
+ * before the unit; if any test is false the whole unit is kept: keep[r] = 1 for
+ * its reads, which are consumed raw (consume(), src/oxli/hashtable.cc:280-294)
+ * in order.  Tables, n_unique_kmers, n_occupied and bigcounts equal the
+ * sequential loop's when the call returns.  Reads shorter than k get
+ * status[r] = 1 and keep[r] = 0, are never consumed and take no part in their
+ * unit's decision (the reference's reader drops them, khmer/utils.py:219-229).
+ * The device decides windows of window_units units by at most max_iters
+ * fixed-point iterations each (0: the defaults); both change only the
+ * schedule, never a result.  stats (nullable) receives {windows, iterations,
+ * candidate units, records}.  Byte, Nibble and Bit storage, both hash
+ * families; KH_EVALUE for a shard of a group. */
+int kh_normalize_by_median(kh_graph *g, const char *seqs, const uint64_t *offsets, uint64_t nreads,
+                           const uint8_t *pair_with_next /* nullable; 1: reads r and r+1 are one unit */,
+                           uint32_t cutoff, uint32_t window_units, uint32_t max_iters /* 0: defaults */,
+                           uint8_t *keep, uint8_t *status, uint64_t *stats /* nullable, [4] */);
 /* Hashtable::trim_on_abundance (below = 0, src/oxli/hashtable.cc:504-533) or
  * trim_below_abundance (below = 1, hashtable.cc:535-563) per raw read of a
  * batch: trim_at[r] = 0 when the read has a single k-mer or its first k-mer

@@ -93,6 +93,8 @@ SIGNATURES = {
     "kh_graph_kmer_counts": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.POINTER(ctypes.c_uint16), PU64]),
     "kh_median_at_least": (i32, [P, ctypes.c_char_p, PU64, u64, u32, ctypes.POINTER(ctypes.c_uint8),
                                  ctypes.POINTER(ctypes.c_uint8)]),
+    "kh_normalize_by_median": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.POINTER(ctypes.c_uint8), u32, u32, u32,
+                                     ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), PU64]),
     "kh_trim_on_abundance": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.c_uint16, i32, i32, u32, PU64,
                                    ctypes.POINTER(ctypes.c_uint8)]),
     "kh_find_spectral_error_positions": (i32, [P, ctypes.c_char_p, PU64, u64, ctypes.c_uint16, PU64, PU32, u64,

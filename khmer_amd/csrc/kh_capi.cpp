@@ -1037,6 +1037,88 @@ int kh_median_at_least(kh_graph *h, const char *seqs, const uint64_t *offsets, u
     });
 }
 
+// scripts/normalize-by-median.py:155-179.  The reads >= k bases are packed unit
+// by unit; a chunk of units (cut at the graph's batch size) goes through one
+// of three paths: the device fixed point (engine_diginorm), "keep everything"
+// when no count of this storage can reach the cutoff, or the unit-by-unit loop
+// when only bigcount values can (Byte storage, bigcount on, cutoff > 255).
+int kh_normalize_by_median(kh_graph *h, const char *seqs, const uint64_t *offsets, uint64_t nreads,
+                           const uint8_t *pair_with_next, uint32_t cutoff, uint32_t window_units, uint32_t max_iters,
+                           uint8_t *keep, uint8_t *status, uint64_t *stats) {
+    return guard([&] {
+        CHECK_PTR(h);
+        Graph *g = h->g;
+        std::lock_guard<std::recursive_mutex> lk(g->mu);
+        KH_HIP(hipSetDevice(g->device));
+        if (g->world != 1 || g->grouped) fail(KH_EVALUE, "normalize-by-median does not take a shard of a group");
+        if (stats) std::fill(stats, stats + 4, (uint64_t)0);
+        const uint32_t max_count = g->kind == BIT ? 1 : (g->kind == NIBBLE ? 15 : 255);
+        const bool beyond = cutoff > max_count;
+        const bool slow = beyond && g->kind == BYTE && g->use_bigcount;
+        const uint64_t chunk_kmers = std::min<uint64_t>(g->batch_kmers, 1ull << 26);
+
+        HostBatch b;
+        b.hash = g->hash;
+        std::vector<uint32_t> uoff{0};
+        std::vector<uint64_t> ufirst;    // first read of each unit of the chunk
+        std::vector<uint8_t> ucount, ukeep;
+        auto flush = [&] {
+            const size_t nu = ufirst.size();
+            if (!nu) return;
+            ukeep.assign(nu, 0);
+            if (!beyond) {
+                engine_diginorm(g, b, uoff, cutoff, window_units, max_iters, ukeep.data(), stats);
+            } else {
+                // median_at_least is false for every read: all units with a read are kept
+                for (size_t u = 0; u < nu; u++) ukeep[u] = uoff[u + 1] > uoff[u];
+                engine_consume_host(g, b, nullptr);
+                if (stats) stats[0]++;
+            }
+            for (size_t u = 0; u < nu; u++)
+                for (uint64_t r = ufirst[u]; r < ufirst[u] + ucount[u]; r++) keep[r] = ukeep[u] && !status[r];
+            b.clear();
+            uoff.assign(1, 0);
+            ufirst.clear();
+            ucount.clear();
+        };
+
+        for (uint64_t r = 0; r < nreads;) {
+            const uint64_t nru = pair_with_next && pair_with_next[r] ? 2 : 1;
+            if (r + nru > nreads) fail(KH_EVALUE, "the last read is marked as paired with a following read");
+            if (nru == 2 && pair_with_next[r + 1]) fail(KH_EVALUE, "a read is marked as the mate of two reads");
+            HostBatch ub;   // slow path: this unit alone
+            ub.hash = g->hash;
+            HostBatch &dst = slow ? ub : b;
+            for (uint64_t q = r; q < r + nru; q++) {
+                const char *s = seqs + offsets[q];
+                const size_t len = strnlen(s, (size_t)(offsets[q + 1] - offsets[q]));
+                status[q] = len >= (size_t)g->k ? 0 : 1;
+                keep[q] = 0;
+                if (!status[q]) dst.append(s, len, g->k, false);
+            }
+            if (slow) {
+                // windows of one unit: the test reads the bigcount map as it stands
+                if (ub.nreads()) {
+                    std::vector<uint8_t> res(ub.nreads());
+                    engine_median_at_least(g, ub, cutoff, res.data());
+                    bool kept = false;
+                    for (uint8_t v : res) kept = kept || !v;
+                    if (kept) engine_consume_host(g, ub, nullptr);
+                    for (uint64_t q = r; q < r + nru; q++) keep[q] = kept && !status[q];
+                    if (stats) { stats[0]++; stats[1]++; stats[2] += kept ? 1 : 0; }
+                }
+            } else {
+                uoff.push_back((uint32_t)b.nreads());
+                ufirst.push_back(r);
+                ucount.push_back((uint8_t)nru);
+                if (b.nkmers() >= chunk_kmers || ufirst.size() >= (1u << 30)) flush();
+            }
+            r += nru;
+        }
+        flush();
+    });
+}
+
 int kh_trim_on_abundance(kh_graph *h, const char *seqs, const uint64_t *offsets, uint64_t nreads, uint16_t cutoff,
                          int below, int gate, uint32_t normalize_to, uint64_t *trim_at, uint8_t *status) {
     return guard([&] {

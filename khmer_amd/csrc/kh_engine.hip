@@ -26,10 +26,12 @@
 #include <type_traits>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include "kh_apply.cuh"
+#include "kh_diginorm.cuh"
 #include "kh_internal.h"
 #include "kh_nearprime.cuh"
 #include "kh_query.cuh"
@@ -1782,14 +1784,12 @@ void engine_consume_host(Graph *g, const HostBatch &b, const PassOut *out) {
         consume_reads(g, src_twobit(g, g->ws.d_words), g->ws.d_koff, b.nreads(), b.nkmers(), kpr, out);
 }
 
-void engine_hash_batch(Graph *g, const HostBatch &b, uint64_t *h_out) {
+// hashes of every k-mer of an uploaded host batch into d (device)
+static void batch_hashes(Graph *g, const HostBatch &b, uint64_t *d) {
     const uint64_t nk = b.nkmers(), nr = b.nreads();
-    if (!nk) return;
-    upload_batch(g, b);
-    DevBuf dbuf(nk * 8);
-    uint64_t *d = dbuf.as<uint64_t>();
     const uint64_t tiles = (nk + Q_TILE - 1) / Q_TILE;
     const size_t lds = 16 + (Q_TILE + 2) * 8;
+    if (!tiles) return;
     if (b.hash == MURMUR) {
         SrcBytes s = src_bytes_host(g, b);
         s.koff = g->ws.d_koff;
@@ -1803,6 +1803,15 @@ void engine_hash_batch(Graph *g, const HostBatch &b, uint64_t *h_out) {
                            d);
     }
     KH_HIP(hipGetLastError());
+}
+
+void engine_hash_batch(Graph *g, const HostBatch &b, uint64_t *h_out) {
+    const uint64_t nk = b.nkmers();
+    if (!nk) return;
+    upload_batch(g, b);
+    DevBuf dbuf(nk * 8);
+    uint64_t *d = dbuf.as<uint64_t>();
+    batch_hashes(g, b, d);
     KH_HIP(hipMemcpyAsync(h_out, d, nk * 8, hipMemcpyDeviceToHost, g->stream));
     KH_HIP(hipStreamSynchronize(g->stream));
 }
@@ -1922,6 +1931,224 @@ void engine_median_at_least(Graph *g, const HostBatch &b, uint32_t cutoff, uint8
     KH_HIP(hipGetLastError());
     KH_HIP(hipMemcpyAsync(h_out, b_out.p, nr, hipMemcpyDeviceToHost, g->stream));
     KH_HIP(hipStreamSynchronize(g->stream));
+}
+
+// ---------------------------------------------------------------------------
+// digital normalization (scripts/normalize-by-median.py:155-179)
+// a device buffer that only grows
+struct DnBuf {
+    DevBuf b;
+    uint64_t cap = 0;
+    template <class T> T *need(uint64_t n) {
+        const uint64_t bytes = n * sizeof(T) + 64;
+        if (bytes > cap) {
+            b.alloc(bytes + bytes / 2);
+            cap = bytes + bytes / 2;
+        }
+        return b.as<T>();
+    }
+};
+// the scratch of engine_diginorm, kept with the graph from its first call on
+// (about 45 bytes per record of the largest window, 2^24 records by default),
+// so that a stream of calls does not allocate and free it every time
+struct DnScratch {
+    DnBuf hash, koff, uoff, ge, cand, reads, roff, keys, keys2, vals, vals2, inv, base, heads, kv, S, keep, keep2, tmp,
+        sel, mis;
+};
+
+namespace {
+constexpr uint32_t DN_WINDOW = 65536;          // default units per window (tools/bench_diginorm.py)
+constexpr uint32_t DN_MAX_WINDOW = 1u << 18;   // candidate indices take at most 18 key bits
+constexpr uint32_t DN_ITERS = 32;              // default iteration cap per window
+constexpr uint64_t DN_MAX_RECORDS = 1ull << 24;   // records per window (one unit may exceed it alone)
+
+int bits_for(uint64_t max_value) {   // bits that hold 0 .. max_value
+    int n = 0;
+    while (max_value) { n++; max_value >>= 1; }
+    return n;
+}
+
+unsigned dn_wave_grid(uint64_t waves) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, 16384)); }
+unsigned dn_thread_grid(uint64_t threads) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, 65536)); }
+}  // namespace
+
+// The windowed fixed-point scheme of kh_diginorm.cuh.  Unit u holds packed reads
+// [uoff[u], uoff[u + 1]) of b (reads shorter than k are not in b; a unit may be
+// empty and is then not kept).  cutoff <= the storage's maximum count, so the
+// table bytes alone decide count >= cutoff (a bigcount value is >= 255).
+// h_keep[u] = 1 for the kept units, whose reads are consumed in stream order.
+void engine_diginorm(Graph *g, const HostBatch &b, const std::vector<uint32_t> &uoff, uint32_t cutoff,
+                     uint32_t window_units, uint32_t max_iters, uint8_t *h_keep, uint64_t *stats) {
+    const uint32_t nu = (uint32_t)(uoff.size() - 1);
+    const uint64_t nk = b.nkmers(), nr = b.nreads();
+    std::fill(h_keep, h_keep + nu, (uint8_t)0);
+    if (!nu || !nk) return;
+    if (g->world != 1 || g->grouped) fail(KH_EVALUE, "normalize-by-median does not take a shard of a group");
+    if (uoff[nu] != nr) fail(KH_EVALUE, "unit offsets do not match the batch");
+    const uint32_t W = window_units ? std::min(window_units, DN_MAX_WINDOW) : DN_WINDOW;
+    const uint32_t MI = max_iters ? max_iters : DN_ITERS;
+    const Params &P = g->prm;
+    const uint32_t nt = (uint32_t)P.n;
+    uint64_t maxp = 0;
+    for (uint32_t t = 0; t < nt; t++) maxp = std::max(maxp, P.p[t]);
+    const int bbits = std::max(1, bits_for(maxp - 1)), tbits = bits_for(nt - 1);
+    hipStream_t st = g->stream;
+    auto h2d = [&](void *dst, const void *src, uint64_t bytes) {
+        if (!bytes) return;
+        KH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+        KH_HIP(hipStreamSynchronize(st));
+    };
+    auto d2h = [&](void *dst, const void *src, uint64_t bytes) {
+        if (!bytes) return;
+        KH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+        KH_HIP(hipStreamSynchronize(st));
+    };
+
+    // the batch's hashes, k-mer offsets and unit offsets stay on the device
+    // for the whole call (the consume passes reuse the workspace's staging)
+    upload_batch(g, b);
+    if (!g->dn) g->dn = new DnScratch;
+    DnScratch &m = *g->dn;
+    uint64_t *d_hash = m.hash.need<uint64_t>(nk), *d_koff = m.koff.need<uint64_t>(nr + 1);
+    uint32_t *d_uoff = m.uoff.need<uint32_t>((uint64_t)nu + 1);
+    batch_hashes(g, b, d_hash);
+    h2d(d_koff, b.koff.data(), (nr + 1) * 8);
+    h2d(d_uoff, uoff.data(), (uint64_t)(nu + 1) * 4);
+
+    std::vector<uint8_t> h_cand, h_fin;
+    std::vector<DnRead> reads;
+    std::vector<uint32_t> roff, cunit;
+
+    uint32_t u0 = 0;
+    while (u0 < nu) {
+        // the window: at most W units and DN_MAX_RECORDS records
+        uint32_t u1 = u0;
+        uint64_t wrec = 0;
+        while (u1 < nu && u1 - u0 < W) {
+            const uint64_t kk = (b.koff[uoff[u1 + 1]] - b.koff[uoff[u1]]) * nt;
+            if (u1 > u0 && wrec + kk > DN_MAX_RECORDS) break;
+            wrec += kk;
+            u1++;
+        }
+        if (wrec >= (1ull << 31)) fail(KH_EVALUE, "a unit holds too many k-mers for normalize-by-median");
+        const uint64_t kb = b.koff[uoff[u0]], nkw = b.koff[uoff[u1]] - kb;
+        const uint32_t nuw = u1 - u0;
+        if (stats) stats[0]++;
+        if (!nkw) { u0 = u1; continue; }
+
+        // cheap reject under the table as it stands
+        uint8_t *d_ge = m.ge.need<uint8_t>(nkw), *d_cand = m.cand.need<uint8_t>(nuw);
+        TIMED("dn_ge", hipLaunchKernelGGL(k_dn_ge, dim3(dn_thread_grid(nkw)), dim3(256), 0, st, P, g->d_tab,
+                                           d_hash + kb, (uint32_t)nkw, cutoff, d_ge));
+        TIMED("dn_reject", hipLaunchKernelGGL(k_dn_reject, dim3(dn_wave_grid(nuw)), dim3(256), 0, st, d_uoff + u0, nuw,
+                                               d_koff, kb, d_ge, d_cand));
+        KH_HIP(hipGetLastError());
+        h_cand.resize(nuw);
+        d2h(h_cand.data(), d_cand, nuw);
+
+        // candidate units, their reads and compacted k-mers
+        reads.clear();
+        cunit.clear();
+        roff.assign(1, 0);
+        uint32_t nq = 0;
+        for (uint32_t u = u0; u < u1; u++) {
+            if (!h_cand[u - u0]) continue;
+            for (uint32_t r = uoff[u]; r < uoff[u + 1]; r++) {
+                const uint32_t n = (uint32_t)(b.koff[r + 1] - b.koff[r]);
+                reads.push_back(DnRead{(uint32_t)(b.koff[r] - kb), n, nq, (uint32_t)cunit.size()});
+                nq += n;
+            }
+            cunit.push_back(u);
+            roff.push_back((uint32_t)reads.size());
+        }
+        const uint32_t nc = (uint32_t)cunit.size(), ncr = (uint32_t)reads.size(), nrec = nq * nt;
+        if (stats) { stats[2] += nc; stats[3] += nrec; }
+        if (!nc) { u0 = u1; continue; }
+        const int ubits = std::max(1, bits_for(nc - 1)), end_bit = ubits + bbits + tbits;
+        if (end_bit > 64) fail(KH_EVALUE, "tables too large for the normalize-by-median record keys");
+
+        DnRead *d_reads = m.reads.need<DnRead>(ncr);
+        uint32_t *d_roff = m.roff.need<uint32_t>(nc + 1);
+        h2d(d_reads, reads.data(), (uint64_t)ncr * sizeof(DnRead));
+        h2d(d_roff, roff.data(), (uint64_t)(nc + 1) * 4);
+
+        // records, sorted by (table, bin, candidate), and their run starts
+        uint64_t *d_keys = m.keys.need<uint64_t>(nrec), *d_keys2 = m.keys2.need<uint64_t>(nrec);
+        uint32_t *d_vals = m.vals.need<uint32_t>(nrec), *d_vals2 = m.vals2.need<uint32_t>(nrec);
+        uint32_t *d_inv = m.inv.need<uint32_t>(nrec), *d_kv = m.kv.need<uint32_t>(nrec), *d_S = m.S.need<uint32_t>(nrec);
+        uint8_t *d_base = m.base.need<uint8_t>(nrec);
+        uint64_t *d_heads = m.heads.need<uint64_t>(nrec);
+        TIMED("dn_records", hipLaunchKernelGGL(k_dn_records, dim3(dn_wave_grid(ncr)), dim3(256), 0, st, P, d_hash + kb,
+                                                d_reads, ncr, ubits, bbits, d_keys, d_vals));
+        KH_HIP(hipGetLastError());
+        size_t tb_sort = 0, tb_scan = 0, tb_sum = 0;
+        KH_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, d_keys, d_keys2, d_vals, d_vals2, (size_t)nrec, 0u,
+                                         (unsigned)end_bit, st));
+        uint64_t *d_runs = d_keys;   // the unsorted keys are free after the sort
+        KH_HIP(rocprim::inclusive_scan(nullptr, tb_scan, d_heads, d_runs, (size_t)nrec, DnMax2(), st));
+        KH_HIP(rocprim::exclusive_scan(nullptr, tb_sum, d_kv, d_S, 0u, (size_t)nrec, rocprim::plus<uint32_t>(), st));
+        const size_t tb = std::max(tb_sort, std::max(tb_scan, tb_sum));
+        void *d_tmp = m.tmp.need<uint8_t>(tb);
+        TIMED("dn_sort", KH_HIP(rocprim::radix_sort_pairs(d_tmp, tb_sort, d_keys, d_keys2, d_vals, d_vals2,
+                                                          (size_t)nrec, 0u, (unsigned)end_bit, st)));
+        TIMED("dn_heads", hipLaunchKernelGGL(k_dn_heads, dim3(dn_thread_grid(nrec)), dim3(256), 0, st, P, g->d_tab,
+                                              d_keys2, d_vals2, nrec, ubits, bbits, d_inv, d_base, d_heads));
+        KH_HIP(hipGetLastError());
+        KH_HIP(rocprim::inclusive_scan(d_tmp, tb_scan, d_heads, d_runs, (size_t)nrec, DnMax2(), st));
+
+        // fixed point of keep, from all ones
+        uint8_t *d_keep = m.keep.need<uint8_t>(nc), *d_keep2 = m.keep2.need<uint8_t>(nc);
+        uint32_t *d_mis = m.mis.need<uint32_t>(1);
+        KH_HIP(hipMemsetAsync(d_keep, 1, nc, st));
+        const uint32_t umask = (uint32_t)((1ull << ubits) - 1);
+        uint32_t ncommit = 0;
+        for (uint32_t it = 1;; it++) {
+            uint32_t mis = nc;
+            h2d(d_mis, &mis, 4);
+            TIMED("dn_iter", {
+                hipLaunchKernelGGL(k_dn_kv, dim3(dn_thread_grid(nrec)), dim3(256), 0, st, d_keys2, nrec, umask, d_keep,
+                                   d_kv);
+                KH_HIP(rocprim::exclusive_scan(d_tmp, tb_sum, d_kv, d_S, 0u, (size_t)nrec, rocprim::plus<uint32_t>(),
+                                               st));
+                hipLaunchKernelGGL(k_dn_iter, dim3(dn_wave_grid(nc)), dim3(256), 0, st, P.kind, (int)nt, d_roff,
+                                   d_reads, nc, d_inv, d_base, d_runs, d_S, cutoff, d_keep, d_keep2, d_mis);
+            });
+            KH_HIP(hipGetLastError());
+            d2h(&mis, d_mis, 4);
+            if (stats) stats[1]++;
+            std::swap(d_keep, d_keep2);   // d_keep: the newest flags
+            // units [0, mis) agree in both iterates, so they are final; unit
+            // mis was computed from them alone, so its new flag is final too
+            if (mis >= nc) { ncommit = nc; break; }
+            if (it >= MI) { ncommit = mis + 1; break; }
+        }
+        h_fin.resize(ncommit);
+        d2h(h_fin.data(), d_keep, ncommit);
+
+        // commit: consume the kept units' reads in stream order
+        reads.erase(std::remove_if(reads.begin(), reads.end(),
+                                   [&](const DnRead &r) { return r.unit >= ncommit || !h_fin[r.unit]; }),
+                    reads.end());
+        uint32_t nsel = 0;
+        for (DnRead &r : reads) {
+            r.q0 = nsel;
+            nsel += r.n;
+        }
+        for (uint32_t c = 0; c < ncommit; c++)
+            if (h_fin[c]) h_keep[cunit[c]] = 1;
+        if (nsel) {
+            uint64_t *d_sel = m.sel.need<uint64_t>(nsel);
+            h2d(d_reads, reads.data(), reads.size() * sizeof(DnRead));
+            TIMED("dn_gather", hipLaunchKernelGGL(k_dn_gather, dim3(dn_wave_grid(reads.size())), dim3(256), 0, st,
+                                                   d_hash + kb, d_reads, (uint32_t)reads.size(), d_sel));
+            KH_HIP(hipGetLastError());
+            engine_consume_hashes(g, d_sel, nsel, nullptr);
+            KH_HIP(hipStreamSynchronize(st));
+        }
+        u0 = ncommit == nc ? u1 : cunit[ncommit];
+    }
+    KH_HIP(hipStreamSynchronize(st));
+    engine_collect_events(g);
 }
 
 void engine_median(Graph *g, const HostBatch &b, uint16_t *med, float *avg, float *sd) {
@@ -2327,6 +2554,7 @@ Graph *graph_create(int kind, int hash, int k, const uint64_t *sizes, int n, int
 Graph::~Graph() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    delete dn;
     Workspace &w = ws;
     void *ptrs[] = {d_tab, d_bc_keys, d_bc_vals, w.rec1, w.rec2, w.fullf, w.newbits, w.bc, w.bcn, w.bck, w.bcv,
                     w.off1, w.ch2, w.off2, w.mcnt, w.moff, w.scan_tmp, w.wcnt, w.xseg, w.reg_base, w.reg_cur, w.bkt_base, w.bkt_cur, w.ctr, w.d_words, w.d_koff, w.d_bytes,

@@ -250,6 +250,8 @@ class TagSet {
     std::vector<uint64_t> sorted() const;   // ascending (std::set order)
 };
 
+struct DnScratch;   // normalize-by-median scratch (kh_engine.hip)
+
 struct Graph {
     int kind = BYTE, hash = TWOBIT, k = 0, n = 0, device = 0;
     std::vector<uint64_t> sizes, nbytes;
@@ -284,6 +286,7 @@ struct Graph {
     // counts far wider than Poisson
     double cap_sigma = 8.0;
     Workspace ws;
+    DnScratch *dn = nullptr;          // engine_diginorm's buffers, kept across calls
     // optional per-kernel HIP-event timing (kh_graph_set_profiling)
     bool profile = false;
     struct KStat { double ms = 0; uint64_t n = 0; };
@@ -384,6 +387,14 @@ uint64_t engine_consume_filtered(Graph *g, const HostBatch &b, const BandMask &f
 void engine_median(Graph *g, const HostBatch &b, uint16_t *med, float *avg, float *sd);
 void engine_kmer_counts(Graph *g, const HostBatch &b, uint16_t *h_out);
 void engine_median_at_least(Graph *g, const HostBatch &b, uint32_t cutoff, uint8_t *h_out);
+// digital normalization of a batch (scripts/normalize-by-median.py:155-179):
+// unit u holds packed reads [uoff[u], uoff[u + 1]) of b; cutoff must not exceed
+// the storage's maximum count.  h_keep[u] = 1 for kept units, whose reads are
+// consumed in stream order before the call returns; window_units / max_iters
+// (0: defaults) only change the schedule.  stats (nullable, [4]) accumulates
+// {windows, iterations, candidate units, records}.
+void engine_diginorm(Graph *g, const HostBatch &b, const std::vector<uint32_t> &uoff, uint32_t cutoff,
+                     uint32_t window_units, uint32_t max_iters, uint8_t *h_keep, uint64_t *stats);
 void engine_hash_batch(Graph *g, const HostBatch &b, uint64_t *h_out);
 void engine_median_fixed_device(Graph *g, const void *d_reads, uint64_t nreads, uint64_t read_len, uint16_t *d_med,
                                 float *d_avg, float *d_sd);

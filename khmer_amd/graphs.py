@@ -294,6 +294,48 @@ class Hashtable(object):
                                      out, st))
         return [None if st[i] else bool(out[i]) for i in range(n)]
 
+    def normalize_by_median_batch(self, sequences, cutoff, pairs=None, window=0, max_iters=0, stats=None,
+                                  allow_short=False):
+        """Digital normalization of a batch on the device, the loop of
+        scripts/normalize-by-median.py:155-179: for each unit in order (a read,
+        or reads i and i + 1 where pairs[i] is true), the unit is kept when
+        median_at_least(read, cutoff) is false for any of its reads against
+        the table as it stands before the unit, and a kept unit's reads are
+        consume()d.  Returns one bool per read: its unit was kept.
+
+        `window` (units decided together) and `max_iters` (fixed-point
+        iterations per window) only change the schedule; 0 takes the defaults.
+        A dict passed as `stats` gets the call's windows, iterations,
+        candidates and records added to its entries.  A read shorter than k
+        raises ValueError before anything is consumed; with `allow_short` it
+        gives None instead, is not consumed and takes no part in its unit's
+        decision."""
+        datas, offs = self._pack_reads(sequences)
+        n = len(datas)
+        if not n:
+            return []
+        if not allow_short:
+            for d in datas:
+                if len(d) < self._k:
+                    raise ValueError("sequence length ({}) must >= the hashtable k-mer size ({})".format(
+                        len(d), self._k))
+        pw = None
+        if pairs is not None:
+            if len(pairs) != n:
+                raise ValueError("pairs must hold one flag per read")
+            pw = (ctypes.c_uint8 * n)(*[1 if p else 0 for p in pairs])
+        keep = (ctypes.c_uint8 * n)()
+        st = (ctypes.c_uint8 * n)()
+        cst = (ctypes.c_uint64 * 4)()
+        rc = lib.kh_normalize_by_median(self._g, b"".join(datas), _u64_array(offs), n, pw,
+                                        int(cutoff) & 0xFFFFFFFF, int(window), int(max_iters), keep, st, cst)
+        self._refresh_mirrors()
+        check(rc)
+        if stats is not None:
+            for key, v in zip(("windows", "iterations", "candidates", "records"), cst):
+                stats[key] = stats.get(key, 0) + v
+        return [None if st[i] else bool(keep[i]) for i in range(n)]
+
     # ---- abundance trimming (graphs.pyx:197-214) ----
     @staticmethod
     def _pack_reads(sequences):

@@ -188,8 +188,38 @@ def create_nodegraph(args, ksize=None, multiplier=1.0, fp_rate=0.01):
     return khmer_amd.Nodegraph(ksize, size, args.n_tables)
 
 
+def check_conflicting_args(args, graphtype):
+    """With -l/--loadgraph the saved table decides k, the number of tables
+    and their size: warn when the command line also sets them, or asks for
+    automatic sizing, and take the file's values (khmer_args.py:225-272)."""
+    if getattr(args, "quiet", None):
+        configure_logging(args.quiet)
+    if not getattr(args, "loadgraph", None):
+        return
+    defaults = {"ksize": DEFAULT_K, "n_tables": DEFAULT_N_TABLES, "max_tablesize": DEFAULT_MAX_TABLESIZE}
+    if any(getattr(args, key, value) != value for key, value in defaults.items()):
+        log_warn("\n*** WARNING: You are loading a saved k-mer countgraph from\n"
+                 "*** {hashfile}, but have set k-mer table parameters.\n"
+                 "*** Your values for ksize, n_tables, and tablesize\n"
+                 "*** will be ignored.", hashfile=args.loadgraph)
+    if any(getattr(args, key, None) for key in ("unique_kmers", "max_memory_usage")):
+        log_warn("\n*** WARNING: You have asked that the graph size be automatically calculated\n"
+                 "*** (by using -U or -M).\n"
+                 "*** But you are loading an existing graph!\n"
+                 "*** Size will NOT be set automatically.")
+    if graphtype in ("countgraph", "smallcountgraph"):
+        import khmer_amd
+        info = khmer_amd.extract_countgraph_info(args.loadgraph)
+        args.ksize = info.ksize
+        args.n_tables = info.n_tables
+        args.max_tablesize = info.table_size
+        if info.ht_type == khmer_amd.FILETYPES["SMALLCOUNT"]:
+            args.small_count = True
+
+
 def report_on_config(args, graphtype="countgraph"):
     """Print the table parameters and memory estimate (khmer_args.py:587-617)."""
+    check_conflicting_args(args, graphtype)
     if getattr(args, "quiet", None):
         configure_logging(args.quiet)
     bpb = _buckets_per_byte()
@@ -279,6 +309,12 @@ def build_nodegraph_args(descr=None, epilog=None, parser=None, citations=None):
     return build_graph_args(descr=descr, epilog=epilog, parser=parser, citations=citations)
 
 
+def add_loadgraph_args(parser):
+    """-l / --loadgraph (khmer_args.py:491-494)."""
+    parser.add_argument("-l", "--loadgraph", metavar="filename", default=None,
+                        help="load a precomputed k-mer graph from disk")
+
+
 def add_threading_args(parser):
     parser.add_argument("-T", "--threads", default=DEFAULT_N_THREADS, type=int,
                         help="Accepted for compatibility; the device consumes each file "
@@ -314,6 +350,34 @@ def check_input_files(file_path, force):
         if not force:
             print("NOTE: This can be overridden using the --force argument", file=sys.stderr)
             sys.exit(1)
+
+
+def check_valid_file_exists(in_files):
+    """Warn about empty or missing inputs where some may be either; the check
+    ends at the first good file (khmer/kfile.py:185-205)."""
+    import stat as _stat
+    for in_file in in_files:
+        if in_file == "-":
+            continue
+        if os.path.exists(in_file):
+            st = os.stat(in_file)
+            if st.st_size > 0 or _stat.S_ISBLK(st.st_mode) or _stat.S_ISFIFO(st.st_mode):
+                return
+            print("WARNING: Input file %s is empty" % in_file, file=sys.stderr)
+        else:
+            print("WARNING: Input file %s not found" % in_file, file=sys.stderr)
+
+
+def describe_file_handle(handle):
+    """The file's name, or "block device" for stdout, stdin and device files
+    (khmer/kfile.py:208-222)."""
+    import stat as _stat
+    if handle in (sys.stdout, sys.stdin, getattr(sys.stdout, "buffer", None), getattr(sys.stdin, "buffer", None)):
+        return "block device"
+    mode = os.stat(handle.name).st_mode
+    if _stat.S_ISBLK(mode) or _stat.S_ISCHR(mode):
+        return "block device"
+    return handle.name
 
 
 def check_file_writable(file_path):

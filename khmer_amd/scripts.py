@@ -5,7 +5,11 @@
 scripts/load-graph.py (reference scripts/load-graph.py + oxli/build_graph.py:
 40-123) and `filter_abund(argv)` is scripts/filter-abund.py (reference
 scripts/filter-abund.py:68-168; it trims FILTER_BATCH_READS reads per device
-pass instead of one call per read, and spools stdin to a temporary file).
+pass instead of one call per read, and spools stdin to a temporary file);
+`normalize_by_median(argv)` is scripts/normalize-by-median.py (reference
+scripts/normalize-by-median.py:72-419; NORMALIZE_BATCH_READS reads per device
+call of Hashtable.normalize_by_median_batch, the progress report replayed
+from the keep flags).
 Options, stderr messages, the saved table, the `.info` file, the
 `.info.json` / `.info.tsv` summaries and the `.tagset` file match the
 reference's.  Each input file is consumed as the reference does it: `-T`
@@ -356,6 +360,299 @@ def filter_abund(argv=None):
         KA.log_info("output in {outfile}", outfile=outfile)
     if args.single_output_file:
         close_out(raw, outfp)
+    return 0
+
+
+# ---------------------------------------------------------------------------
+# normalize-by-median.py
+
+DEFAULT_DESIRED_COVERAGE = 20
+NORMALIZE_BATCH_READS = 1 << 16     # reads per device call of normalize_by_median
+
+_NBM_EPILOG = """\
+    Discard sequences based on whether or not their median k-mer abundance lies
+    above a specified cutoff. Kept sequences will be placed in <fileN>.keep.
+
+    By default, paired end reads will be considered together; if either read
+    should be kept, both will be kept.  Unpaired reads are treated
+    individually.  With -p/--paired proper pairing is required and the script
+    exits on unpaired reads; --unpaired-reads names a file of orphan reads
+    to be read after the paired ones.  --force_single ignores all pairing
+    information.
+
+    -s/--savegraph saves the k-mer countgraph after all sequences have been
+    processed; -l/--loadgraph loads one before processing.  The files are those
+    of load-into-counting.py.
+
+    Example:
+
+        normalize-by-median.py -k 17 -C 20 -p reads.pe.fq
+    """
+
+
+def normalize_by_median_parser():
+    parser = KA.build_counting_args(descr="Do digital normalization (remove mostly redundant sequences)",
+                                    epilog=KA.dedent(_NBM_EPILOG), citations=["diginorm"])
+    parser.prog = "normalize-by-median.py"
+    parser.add_argument("-q", "--quiet", dest="quiet", default=False, action="store_true")
+    parser.add_argument("-C", "--cutoff", type=KA.check_argument_range(0, 256, "cutoff"),
+                        default=DEFAULT_DESIRED_COVERAGE,
+                        help="when the median k-mer coverage level is above this number the read is not kept.")
+    parser.add_argument("-p", "--paired", action="store_true",
+                        help="require that all sequences be properly paired")
+    parser.add_argument("--force_single", dest="force_single", action="store_true",
+                        help="treat all sequences as single-ended/unpaired")
+    parser.add_argument("-u", "--unpaired-reads", metavar="unpaired_reads_filename",
+                        help="include a file of unpaired reads to which -p/--paired does not apply.")
+    parser.add_argument("-s", "--savegraph", metavar="filename", default=None,
+                        help="save the k-mer countgraph to disk after all reads are loaded.")
+    parser.add_argument("-R", "--report", metavar="report_filename",
+                        help="write progress report to report_filename")
+    parser.add_argument("--report-frequency", metavar="report_frequency", type=int, default=100000,
+                        help="report progress every report_frequency reads")
+    parser.add_argument("-f", "--force", dest="force", action="store_true",
+                        help="continue past file reading errors")
+    parser.add_argument("-o", "--output", metavar="filename", default=None, dest="single_output_file",
+                        help="only output a single file with the specified filename; use a single dash \"-\" "
+                             "to specify that output should go to STDOUT (the terminal)")
+    parser.add_argument("input_filenames", metavar="input_sequence_filename", nargs="+",
+                        help="Input FAST[AQ] sequence filename.")
+    KA.add_loadgraph_args(parser)
+    KA.add_output_compression_type(parser)
+    return parser
+
+
+class DiginormProgress(object):
+    """The running total / kept counts of normalize-by-median.py and the
+    points at which it reports them (scripts/normalize-by-median.py:72-152).
+    The reference looks at the counts after every unit; here whole batches
+    come back from the device, so advance() replays a batch's units from
+    their keep flags and returns the (total, kept) pairs of every report due,
+    the same ones the one-unit-at-a-time loop would give."""
+
+    def __init__(self, report_frequency=100000):
+        self.total = 0
+        self.kept = 0
+        self.report_frequency = report_frequency
+        self.next_report_at = report_frequency
+        self.last_report_at = report_frequency
+
+    def advance(self, unit_sizes, unit_kept):
+        due = []
+        for size, kept in zip(unit_sizes, unit_kept):
+            self.total += size
+            if kept:
+                self.kept += size
+            if self.total >= self.next_report_at:
+                self.next_report_at += self.report_frequency
+                self.last_report_at = self.total
+                due.append((self.total, self.kept))
+        return due
+
+
+def report_line(total, kept):
+    """One line of the -R report (scripts/normalize-by-median.py:125-128)."""
+    return "{total},{kept},{f_kept:.4}".format(total=total, kept=kept, f_kept=kept / float(total))
+
+
+def _clean_input_reads(records):
+    """khmer/utils.py:158-168: upper case, N -> A, as a plain attribute."""
+    for record in records:
+        record.cleaned = record.sequence.upper().replace("N", "A")
+        yield record
+
+
+class _NoReads(object):
+    """Stands in for the parser of an empty input file."""
+
+    def __iter__(self):
+        return iter(())
+
+    def close(self):
+        pass
+
+
+def normalize_by_median_args(argv=None):
+    """Parsed options; -p with --force_single is refused (the reference stops
+    on it with broken_paired_reader's ValueError at its first input)."""
+    args = normalize_by_median_parser().parse_args(argv)
+    if args.force_single and args.paired:
+        KA.log_error("** ERROR: force_single and require_paired cannot both be set!")
+        KA.log_error("** Exiting!")
+        sys.exit(1)
+    return args
+
+
+def normalize_by_median(argv=None):
+    import khmer_amd
+    from .utils import broken_paired_reader
+    args = normalize_by_median_args(argv)
+    KA.configure_logging(args.quiet)
+    KA.report_on_config(args)
+
+    report_fp = open(args.report, "w") if args.report else None
+    filenames = list(args.input_filenames)
+    if not args.single_output_file:
+        basenames = set()
+        for name in filenames:
+            base = os.path.basename(name)
+            if base in basenames:
+                KA.log_error("ERROR: Duplicate filename--Cannot handle this!")
+                KA.log_error("** Exiting!")
+                sys.exit(1)
+            basenames.add(base)
+
+    KA.check_valid_file_exists(filenames)
+    KA.check_space(filenames, args.force)
+    if args.savegraph is not None:
+        KA.check_space_for_graph(args.savegraph, KA.calculate_graphsize(args, "countgraph"), args.force)
+
+    if args.loadgraph:
+        KA.log_info("loading k-mer countgraph from {graph}", graph=args.loadgraph)
+        countgraph = khmer_amd.Countgraph.load(args.loadgraph)
+    else:
+        KA.log_info("making countgraph")
+        countgraph = KA.create_countgraph(args)
+    ksize = countgraph.ksize()
+
+    progress = DiginormProgress(args.report_frequency)
+    if report_fp:
+        report_fp.write("total,kept,f_kept\n")
+
+    files = [(name, args.paired) for name in filenames]
+    if args.unpaired_reads:
+        files.append((args.unpaired_reads, False))
+
+    def open_out(name):
+        raw = sys.stdout.buffer if name == "-" else open(name, "wb")
+        return raw, KA.get_file_writer(raw, args.gzip, args.bzip)
+
+    def close_out(raw, outfp):
+        if outfp is not raw:
+            outfp.close()        # the compressor's trailer
+        if raw is not sys.stdout.buffer:
+            raw.close()
+        else:
+            raw.flush()
+
+    raw = outfp = None
+    if args.single_output_file:
+        raw, outfp = open_out(args.single_output_file)
+    elif "-" in filenames or "/dev/stdin" in filenames:
+        print("Accepting input from stdin; output filename must be provided with '-o'.", file=sys.stderr)
+        sys.exit(1)
+
+    def normalize_batch(units, filename):
+        """One device call over the batch's units; writes the kept records."""
+        if not units:
+            return
+        seqs, pairs = [], []
+        for unit in units:
+            for i, rec in enumerate(unit):
+                seqs.append(rec.cleaned)
+                pairs.append(i + 1 < len(unit))
+        flags = countgraph.normalize_by_median_batch(seqs, args.cutoff, pairs=pairs)
+        unit_kept, at = [], 0
+        for unit in units:
+            unit_kept.append(flags[at])
+            if flags[at]:
+                for rec in unit:
+                    write_record(rec, outfp)
+            at += len(unit)
+        for total, kept in progress.advance([len(u) for u in units], unit_kept):
+            KA.log_info("... kept {kept} of {tot} or {perc_kept:.1%} sofar", kept=kept, tot=total,
+                        perc_kept=kept / float(total))
+            KA.log_info("... in file {name}", name=filename)
+            if report_fp:
+                print(report_line(total, kept), file=report_fp)
+                report_fp.flush()
+
+    def normalize_file(filename, require_paired):
+        reads_start = progress.total
+        spool = None
+        if filename in ("-", "/dev/stdin"):    # the parser wants a file it can reopen: spool the pipe
+            spool = tempfile.NamedTemporaryFile(prefix="normalize-by-median-stdin-")
+            shutil.copyfileobj(sys.stdin.buffer, spool)
+            spool.flush()
+        else:
+            open(filename, "rb").close()       # a missing input fails here, with the system's message
+        # an empty file is no error here: it is reported as SKIPPED below
+        # (the parser itself refuses a file without sequences)
+        empty = not spool and os.path.isfile(filename) and os.path.getsize(filename) == 0
+        parser = _NoReads() if empty else khmer_amd.ReadParser(spool.name if spool else filename)
+        units, nreads = [], 0
+        try:
+            reader = broken_paired_reader(_clean_input_reads(parser), min_length=ksize,
+                                          force_single=args.force_single, require_paired=require_paired)
+            while True:
+                try:
+                    _, is_pair, read1, read2 = next(reader)
+                except StopIteration:
+                    break
+                except Exception:
+                    # the units read before the error are normalized and written, as by
+                    # the reference's one-unit-at-a-time loop
+                    normalize_batch(units, filename)
+                    raise
+                units.append((read1, read2) if is_pair else (read1,))
+                nreads += len(units[-1])
+                if nreads >= NORMALIZE_BATCH_READS:
+                    normalize_batch(units, filename)
+                    units, nreads = [], 0
+            normalize_batch(units, filename)
+        finally:
+            parser.close()
+            if spool:
+                spool.close()
+        if progress.total == reads_start:
+            KA.log_info("SKIPPED empty file {name}", name=filename)
+        else:
+            KA.log_info("DONE with {inp}; kept {kept} of {total} or {perc_kept:.1%}", inp=filename,
+                        kept=progress.kept, total=progress.total,
+                        perc_kept=progress.kept / float(progress.total))
+        if report_fp and progress.total != progress.last_report_at:
+            print(report_line(progress.total, progress.kept), file=report_fp)
+            report_fp.flush()
+
+    corrupt_files = []
+    for filename, require_paired in files:
+        if not args.single_output_file:
+            output_name = os.path.basename(filename) + ".keep"
+            raw, outfp = open_out(output_name)
+        try:
+            normalize_file(filename, require_paired)
+            KA.log_info("output in {name}", name=KA.describe_file_handle(raw))
+            if not args.single_output_file:
+                close_out(raw, outfp)
+        except (IOError, OSError, ValueError) as error:
+            KA.log_error("** ERROR: {error}", error=str(error))
+            KA.log_error("** Failed on {name}: ", name=filename)
+            if not args.single_output_file:
+                close_out(raw, outfp)
+                os.remove(output_name)
+            if not args.force:
+                KA.log_error("** Exiting!")
+                sys.exit(1)
+            KA.log_error("*** Skipping error file, moving on...")
+            corrupt_files.append(filename)
+    if args.single_output_file:
+        close_out(raw, outfp)
+
+    KA.log_info("Total number of unique k-mers: {umers}", umers=countgraph.n_unique_kmers())
+    if args.savegraph is not None:
+        KA.log_info("...saving to {name}", name=args.savegraph)
+        countgraph.save(args.savegraph)
+
+    # for max_false_pos see Zhang et al., http://arxiv.org/abs/1309.2975
+    fp_rate = khmer_amd.calc_expected_collisions(countgraph, False, max_false_pos=.8)
+    KA.log_info("fp rate estimated to be {fpr:1.3f}", fpr=fp_rate)
+
+    if args.force and corrupt_files:
+        KA.log_error("** WARNING: Finished with errors!")
+        KA.log_error("** I/O Errors occurred in the following files:")
+        KA.log_error("\t" + " ".join(corrupt_files))
+    if report_fp:
+        report_fp.close()
     return 0
 
 
