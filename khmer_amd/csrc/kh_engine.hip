@@ -566,6 +566,9 @@ static uint64_t bkt_plan(Graph *g, uint64_t nkmers) {
 // scale); KH_NEAR_PRIME=0 keeps the per-table level 1 (read in every build:
 // the tests compare both paths).
 static bool np_enabled() { return test_env_int("KH_NEAR_PRIME", 1) != 0; }
+// level-2 table groups (n2_launch); KH_N2_TG=0 keeps one group of all the
+// tables (read per pass in every build: the tests compare both kernels)
+static int np_n2_tg() { return test_env_int("KH_N2_TG", 2); }
 // magic division check: (rho * magic) >> 32 == rho / d for every rho < n
 static bool np_magic_ok(uint64_t n, uint32_t d, uint32_t magic) {
     for (uint64_t rho = 0; rho < n; rho++)
@@ -1450,14 +1453,16 @@ static PassState pass_stage_a(Graph *g, const Src &src, uint64_t nkmers, bool ap
                 const NPGeo fg = np_fine_geo(npg, npf);
                 const uint32_t nparts = l2f_parts(fg.nb);
                 const uint64_t fofs = (npg.cap * npg.nb + 63) & ~63ull;
-                TIMED("scatter_n2", hipLaunchKernelGGL(n2_kernel(fg.n), dim3(fg.nb * nparts), dim3(PT_THREADS),
-                                                       lds_scatter_n2(fg), st, fg, nparts, w.np_fcur, nullptr,
+                const N2Launch n2 = n2_launch(fg, np_n2_tg());
+                TIMED("scatter_n2", hipLaunchKernelGGL(n2.fn, dim3(fg.nb * nparts * n2.groups), dim3(n2.threads),
+                                                       n2.lds, st, fg, nparts, w.np_fcur, nullptr,
                                                        l1f_blk_sh(), w.reg_base, (unsigned long long *)w.reg_cur,
                                                        w.rec1 + fofs, w.rec2, w.ctr, l2f_blk_sh()));
             } else if (np) {
                 const uint32_t nparts = l2f_parts(npg.nb);
-                TIMED("scatter_n2", hipLaunchKernelGGL(n2_kernel(npg.n), dim3(npg.nb * nparts), dim3(PT_THREADS),
-                                                       lds_scatter_n2(npg), st, npg, nparts, w.np_cur, w.np_blkj,
+                const N2Launch n2 = n2_launch(npg, np_n2_tg());
+                TIMED("scatter_n2", hipLaunchKernelGGL(n2.fn, dim3(npg.nb * nparts * n2.groups), dim3(n2.threads),
+                                                       n2.lds, st, npg, nparts, w.np_cur, w.np_blkj,
                                                        l1f_blk_sh(), w.reg_base, (unsigned long long *)w.reg_cur,
                                                        w.rec1, w.rec2, w.ctr, l2f_blk_sh()));
             } else {
@@ -2469,9 +2474,10 @@ static void set_lds_limits() {
     KH_LDS_MAX((k_scatter_w<PT_THREADS, 2>));
     KH_LDS_MAX((k_scatter_l1p<2>));
     KH_LDS_MAX(k_scatter_n1);
-    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 2>));
-    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 3>));
-    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 4>));
+    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 2, 4>));
+    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 3, 2>));
+    KH_LDS_MAX((k_scatter_n2<PT_THREADS, 4, 2>));
+    KH_LDS_MAX((k_scatter_n2<512, 2, 8>));
     KH_LDS_MAX((k_apply_delta<BYTE, 1024>));
     KH_LDS_MAX((k_apply_delta<NIBBLE, 1024>));
     KH_LDS_MAX((k_apply_delta<BIT, 1024>));

@@ -24,11 +24,15 @@
 //     N region records (j << 32 | bin offset in its 2^s0-bin region): table
 //     i's bins of bucket b lie in its regions [R' b, R' b + R' + E] (E
 //     regions of spill, wrapping past p_i into regions 0 .. E), i.e. N x
-//     Rloc <= 1024 destinations, the same fan-out as k_scatter_l2f.
+//     Rloc <= 1024 destinations, the same fan-out as k_scatter_l2f.  At four
+//     tables a workgroup expands one group of two tables only (2 x Rloc <=
+//     512 destinations: half the LDS, two workgroups a CU) and each bucket
+//     slice is read by both groups' workgroups.
 //
 // Level 1 writes 8 B per k-mer instead of 8 B per (k-mer, table) and does a
 // quarter of the LDS rank atomics, staging and run writes at N = 4; level 2
-// reads a quarter of the records it writes.  The region records, the apply
+// reads a quarter of the records it writes (once per table group: half with
+// its two groups).  The region records, the apply
 // and everything after are unchanged, so the tables and counters are the
 // reference's exactly as before (storage.hh:571-624).
 #pragma once
@@ -339,26 +343,39 @@ __host__ __device__ constexpr size_t lds_n1(size_t F1a) {
 // Level 2: k_scatter_l2f's register-direct scatter (fixed-capacity regions,
 // 64-record blocks, 128-B segments through LDS tails) over a level-1
 // bucket's near-prime records.  Each thread loads IN records (IN / 2 pairs)
-// a tile and expands each into its NT region records (IN * NT <= 8 register
-// slots, NT = N.n); destination d = i Rloc
-// + (region of table i's bin - R' b) (plus table i's regions when the bin
-// wrapped past p_i).  The destination rides in bits [16, 32) of the
-// register copy of the record and is cleared when it is stored.
-template <int THREADS, int NT>
+// a tile and expands each into the region records of its table group.
+//
+// Table groups: the per-destination LDS state (154 B a destination, 128 B of
+// it the 16-record tail) is what limits the workgroups a CU, so the N.n
+// tables are split into N.n / TG groups of TG and a workgroup expands only
+// the tables [t0, t0 + TG) of its bucket slice: TG Rloc destinations, IN
+// level-1 records and IN TG region records per thread a tile.  The grid is
+// buckets x parts x groups with the group index fastest, so the workgroups
+// that read the same slice are dispatched together; every slice is read once
+// per group.  A region is still written by the `parts` workgroups of one
+// bucket (two buckets in the spill regions), all of one group, so reg_plan's
+// slack is unchanged.  Destination d = (i - t0) Rloc + (region of table i's
+// bin - R' b) (plus table i's regions when the bin wrapped past p_i); thread
+// d owns destination d's reservation (THREADS >= TG Rloc, n2_launch).  The
+// destination rides in bits [16, 32) of the register copy of the record and
+// is cleared when it is stored.
+//
+// Instances (n2_launch): four tables run as two groups of two in workgroups
+// of 512 threads with 8 level-1 records (16 region records) a thread -- the
+// tile of the one-group kernel (8192 region records) in half the LDS, two
+// workgroups a CU; two and three tables, and KH_N2_TG=0, run one group of
+// all the tables in 1024 threads with 8 (6) region records a thread.
+template <int THREADS, int TG, int IN>
 __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts, const unsigned long long *bkt_end,
                                                         const uint32_t *blkj, int blk_sh1, const uint64_t *reg_base,
                                                         unsigned long long *reg_cur, const uint64_t *rec_in,
                                                         uint64_t *rec_out, uint64_t *ctr, int blk_sh) {
-#ifndef KH_N2_IN
-#define KH_N2_IN 2   // development A/B: level-1 records per thread a tile at 3-4 tables
-#endif
-    constexpr int IN = NT == 2 ? 2 * KH_N2_IN : KH_N2_IN;   // level-1 records per thread a tile
-    constexpr int RPT = IN * NT <= 8 ? 8 : IN * NT;
+    constexpr int RPT = IN * TG;               // region records per thread a tile
     constexpr int TILE = THREADS * IN;
     constexpr uint32_t SEG = 16;
-    static_assert(NT >= 2 && NT <= NP_MAXT && IN * NT <= RPT, "k_scatter_n2: 2 to 4 tables");
+    static_assert(TG >= 1 && TG <= NP_MAXT && IN % 2 == 0, "k_scatter_n2: 1 to 4 tables a group, pair loads");
     const uint32_t BLK = 1u << blk_sh;
-    const uint32_t F2 = (uint32_t)NT * N.rloc;
+    const uint32_t F2 = (uint32_t)TG * N.rloc;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t *bcur = (uint64_t *)smem;              // [F2]
     uint64_t *nbase = bcur + F2;                    // [F2]
@@ -368,10 +385,22 @@ __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts,
     uint32_t *s_nfl = hist + F2;                    // [1]
     uint16_t *flist = (uint16_t *)(s_nfl + 4);      // [F2]
     if (__builtin_amdgcn_readfirstlane((uint32_t)ctr[CTR_ERR]) & 8u) return;
-    const uint32_t b = blockIdx.x / parts, p = blockIdx.x % parts;
+    const uint32_t groups = (uint32_t)N.n / TG;
+    const uint32_t t0g = (blockIdx.x % groups) * TG;                  // the group's first table
+    const uint32_t slice = blockIdx.x / groups;
+    const uint32_t b = slice / parts, p = slice % parts;
     const uint64_t b0 = (uint64_t)b * N.cap, b1 = min((uint64_t)bkt_end[b], b0 + N.cap);
     const uint64_t len = ((b1 - b0 + parts - 1) / parts + 1) & ~1ull;
     const uint64_t r0 = min(b1, b0 + (uint64_t)p * len), r1 = min(b1, r0 + len);
+    // the group's table constants (uniform)
+    uint64_t gd[TG], gp[TG];
+    uint32_t grt[TG];
+#pragma unroll
+    for (int i = 0; i < TG; i++) {
+        gd[i] = N.d[t0g + i];
+        gp[i] = N.p[t0g + i];
+        grt[i] = N.rt[t0g + i];
+    }
     const uint64_t smask = (1ull << N.s0) - 1;
     const uint64_t omask = (1ull << N.ob) - 1;
     const uint64_t bin0 = (uint64_t)b * ((uint64_t)N.rp << N.s0);   // first bin of the bucket (largest table)
@@ -407,8 +436,8 @@ __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts,
     auto greg = [&](uint32_t d) -> uint64_t {
         const uint32_t i = d / N.rloc;
         uint32_t rho = rb + (d - i * N.rloc);
-        if (rho >= N.rt[i]) rho -= N.rt[i];
-        return (uint64_t)N.rbase[i] + rho;
+        if (rho >= N.rt[t0g + i]) rho -= N.rt[t0g + i];
+        return (uint64_t)N.rbase[t0g + i] + rho;
     };
     uint64_t v[IN];
     uint32_t jb[IN / 2];
@@ -418,7 +447,7 @@ __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts,
         const uint64_t t0 = r0 + (uint64_t)ti * TILE;
         const bool last = ti + 1 == ntiles;
         block_sync();
-        // expand: output slot a * NT + i (k-mer a, table i)
+        // expand: output slot a * TG + i (k-mer a, table t0g + i)
         uint64_t x[RPT];
         uint32_t rank[RPT];
 #pragma unroll
@@ -431,18 +460,18 @@ __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts,
             const uint64_t qv = pay >> N.ob;
             const uint64_t r = bin0 + (pay & omask);
 #pragma unroll
-            for (int i = 0; i < NT; i++) {
-                uint64_t bin = r + qv * N.d[i];
-                if (bin >= N.p[i]) bin -= N.p[i];
+            for (int i = 0; i < TG; i++) {
+                uint64_t bin = r + qv * gd[i];
+                if (bin >= gp[i]) bin -= gp[i];
                 const uint32_t rho = (uint32_t)(bin >> N.s0);
                 int32_t loc = (int32_t)(rho - rb);
-                if (loc < 0) loc += (int32_t)N.rt[i];
+                if (loc < 0) loc += (int32_t)grt[i];
                 if ((uint32_t)loc >= N.rloc) {   // outside the bucket's destinations: a host plan error
                     atomicOr((unsigned long long *)&ctr[CTR_ERR], 16ull);
                     continue;
                 }
                 const uint32_t dst = (uint32_t)i * N.rloc + (uint32_t)loc;
-                x[a * NT + i] = jv | ((uint64_t)dst << 16) | (bin & smask);
+                x[a * TG + i] = jv | ((uint64_t)dst << 16) | (bin & smask);
             }
         }
 #pragma unroll
@@ -530,13 +559,26 @@ __global__ void __launch_bounds__(THREADS) k_scatter_n2(NPGeo N, uint32_t parts,
         rec_out[bcur[d] + sl] = ~0ull;
     }
 }
-static size_t lds_scatter_n2(const NPGeo &N) {
-    return (size_t)N.n * N.rloc * (8 + 8 + 16 * 8 + 4 + 4 + 2) + 16;
-}
+// dests: the destinations of one table group (TG x Rloc)
+static size_t lds_scatter_n2(uint32_t dests) { return (size_t)dests * (8 + 8 + 16 * 8 + 4 + 4 + 2) + 16; }
 using N2Fn = void (*)(NPGeo, uint32_t, const unsigned long long *, const uint32_t *, int, const uint64_t *,
                       unsigned long long *, const uint64_t *, uint64_t *, uint64_t *, int);
-static N2Fn n2_kernel(int n) {
-    return n == 2 ? k_scatter_n2<PT_THREADS, 2> : n == 3 ? k_scatter_n2<PT_THREADS, 3> : k_scatter_n2<PT_THREADS, 4>;
+struct N2Launch {
+    N2Fn fn;
+    uint32_t threads, groups;
+    size_t lds;
+};
+// The level-2 instance of a geometry.  tg (KH_N2_TG): 0 = one group of all
+// the tables; otherwise four tables run as two groups of two.  Three tables
+// (341 destinations a table: a pair does not fit a CU twice) and two stay on
+// one group.
+static N2Launch n2_launch(const NPGeo &N, int tg) {
+    const uint32_t n = (uint32_t)N.n;
+    if (tg != 0 && n == 4 && 2 * N.rloc <= 512) return {k_scatter_n2<512, 2, 8>, 512, 2, lds_scatter_n2(2 * N.rloc)};
+    const N2Fn one = n == 2   ? k_scatter_n2<PT_THREADS, 2, 4>
+                     : n == 3 ? k_scatter_n2<PT_THREADS, 3, 2>
+                              : k_scatter_n2<PT_THREADS, 4, 2>;
+    return {one, (uint32_t)PT_THREADS, 1, lds_scatter_n2(n * N.rloc)};
 }
 
 // ---------------------------------------------------------------------------
